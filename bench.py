@@ -15,6 +15,11 @@ communicator; torch.distributed only bootstraps it and times the job).
 Synthetic data: a seeded random ACGT genome of (all ranks' reads)*150/10 bases (10x coverage);
 reads start uniformly, strand 50/50, 0.1 % substitutions; each read is followed by a '$'
 separator.
+
+A plain run sets up, warms up, times the steps and prints the result line.  --dump-outputs DIR also
+writes what the last timed step returned; --full adds the side measurements and checks after the
+timed steps (the measured copy peak, the host-buffer / FASTA / KMC-file legs, the CPU baseline and the
+parity checks against the oracle).
 """
 import argparse
 import ctypes
@@ -75,11 +80,22 @@ def parse():
     ap.add_argument("--launch-timeout", type=float, default=None,
                     help="seconds the ranks started by --gpus N (no launcher) may run before they are killed "
                          "(default: 900 s + 10 s per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements and checks: the measured copy "
+                         "peak of the roofline, the host-buffer / FASTA / KMC-file legs, the CPU baseline and "
+                         "the parity checks against the oracle (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (W, last, weights, F and whole-array "
+                         "summaries) as DIR/<name>.npy")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check on the CPU: every rank joins a gloo group and rank 0 prints the "
                          "world it saw (no GPU, no build)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.config:
         given = {a.split("=")[0].lstrip("-").replace("-", "_") for a in sys.argv[1:] if a.startswith("--")}
         for key, val in CONFIGS[args.config].items():
@@ -395,6 +411,64 @@ def fasta_path(args, kb, boss, steps, n_reads, files=8):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_SEED = 20141
+DUMP_SAMPLE_ROWS = 3_000_000  # three float32 arrays and the float64 row numbers: 60 MB, a dump may take 64 MB
+
+
+def dump_sample_rows(n, size=None, seed=DUMP_SEED):
+    """The rows of an n-row chunk that --dump-outputs stores: all of them up to `size` (DUMP_SAMPLE_ROWS),
+    else a sorted sample of `size` row numbers (with repeats) from a fixed seed, so equal n gives equal rows."""
+    import numpy as np
+    size = DUMP_SAMPLE_ROWS if size is None else size
+    if n <= size:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, n, size=size, dtype=np.int64))
+
+
+def dump_outputs(out_dir, boss, dc, has_weights, block=64 << 20):
+    """--dump-outputs: the device chunk of the last timed step (what build_device's caller gets: W, last,
+    weights in HBM, F and the row counts) as float .npy files.  W, last and weights are stored at
+    dump_sample_rows(n) (rows.npy, float64); summary.npy (float64, exact below 2^53) covers every row:
+    n, n_real, n_dummy, the number of rows with each W value 0..255, the number of set last flags and the
+    sum of the weights.  The arrays come off the device in `block`-row pieces."""
+    import numpy as np
+    L = boss.lib()
+    n = int(dc.n)
+    rows = dump_sample_rows(n)
+    W = np.empty(len(rows), dtype=np.float32)
+    last = np.empty(len(rows), dtype=np.float32)
+    wt = np.empty(len(rows), dtype=np.float32) if has_weights else None
+    w_hist = np.zeros(256, dtype=np.int64)
+    last_set = 0
+    wt_sum = 0
+    buf = np.empty(min(n, block), dtype=np.uint8)
+    buf32 = np.empty(min(n, block), dtype=np.uint32) if has_weights else None
+    for r0 in range(0, n, block):
+        m = min(block, n - r0)
+        lo, hi = np.searchsorted(rows, [r0, r0 + m])
+        at = rows[lo:hi] - r0
+        L.mtg_memcpy_d2h(buf.ctypes.data, dc.W + r0, m)
+        w_hist += np.bincount(buf[:m], minlength=256)
+        W[lo:hi] = buf[:m][at]
+        L.mtg_memcpy_d2h(buf.ctypes.data, dc.last + r0, m)
+        last_set += int(np.count_nonzero(buf[:m]))
+        last[lo:hi] = buf[:m][at]
+        if has_weights:
+            L.mtg_memcpy_d2h(buf32.ctypes.data, dc.weights + 4 * r0, 4 * m)
+            wt_sum += int(buf32[:m].sum(dtype=np.uint64))
+            wt[lo:hi] = buf32[:m][at]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "W.npy"), W)
+    np.save(os.path.join(out_dir, "last.npy"), last)
+    if has_weights:
+        np.save(os.path.join(out_dir, "weights.npy"), wt)
+    np.save(os.path.join(out_dir, "F.npy"), np.array([int(f) for f in dc.F], dtype=np.float64))
+    np.save(os.path.join(out_dir, "summary.npy"),
+            np.array([n, int(dc.n_real), int(dc.n_dummy)] + [int(c) for c in w_hist] + [last_set, wt_sum],
+                     dtype=np.float64))
+
+
 def measured_copy_peak(torch, boss, device, nbytes=4 << 30, reps=10):
     """Achievable HBM bandwidth on this GPU: the library's copy kernel (mtg_device_copy: one 16-byte
     nontemporal load + store per thread, 6.44 TB/s on the MI355X in tools/copy_bench.hip, which compares
@@ -575,7 +649,7 @@ def main():
         kmers_per_rank = dreads.n_reads
 
     # the achievable-copy denominator, measured before the builds fill HBM with the workspace
-    copy_peak = measured_copy_peak(torch, boss, device) if rank == 0 else None
+    copy_peak = measured_copy_peak(torch, boss, device) if rank == 0 and args.full else None
 
     def step():
         if dreads is not None:
@@ -598,7 +672,11 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = max_over_ranks(time.perf_counter() - t0, world, device)
-    ctor.trim()  # idle workspace blocks back to the device before the host legs build on their own
+    if args.dump_outputs:
+        dump_outputs(os.path.join(args.dump_outputs, "rank%d" % rank) if world > 1 else args.dump_outputs,
+                     boss, dc, bool(args.count_width))
+    if args.full:
+        ctor.trim()  # idle workspace blocks back to the device before the host legs build on their own
     value = job_throughput(kmers_per_rank, world, args.steps, elapsed)
     last = timings[-1]
     # size-independent sanity of the result
@@ -635,6 +713,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -676,7 +755,7 @@ def main():
     if args.kmc:
         result["kmc_input"] = {"records_per_gpu": kmers_per_rank, "write_s": kmc_write_s,
                                "what": "GPU k-mer counter -> KMC1 files (untimed), mtg_kmc_load_device -> HBM"}
-    if rank == 0 and args.host_steps > 0 and world == 1:
+    if args.full and rank == 0 and args.host_steps > 0 and world == 1:
         if args.kmc:
             result["kmc_path"] = kmc_path(args, kb, boss, kmc_base, args.host_steps, kmers_per_rank)
         else:
@@ -692,7 +771,7 @@ def main():
                         "same reads through add_packed + build_chunk (host_path)"}
         if args.fasta_reads > 0:
             result["fasta_path"] = fasta_path(args, kb, boss, args.host_steps, args.fasta_reads)
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         if args.kmc:
             result["cpu_baseline"], sample_parity = cpu_baseline_kmc(args, kb, boss, kmc_base, kmers_per_rank)
             if world == 1:

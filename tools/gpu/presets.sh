@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=${1:-presets}; shift; OUT=gpurun_out/$TAG; mkdir -p $OUT
 P="$@"; [ -z "$P" ] && P="cfg4 cfg5 cfg3"
 for c in $P; do
-  timeout -k 10 420 python -u bench.py --config $c > $OUT/bench_$c.log 2>&1
+  timeout -k 10 420 python -u bench.py --config $c --full > $OUT/bench_$c.log 2>&1
   rc=$?; echo "bench $c rc=$rc"; tail -1 $OUT/bench_$c.log | cut -c1-1500
   [ $rc -ne 0 ] && exit $rc
 done

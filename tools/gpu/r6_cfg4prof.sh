@@ -12,6 +12,6 @@ grep -E "rounds:|carved|dropping" $OUT/cfg4.err | tail -12
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/prof -o cfg4 -- python3 bench.py --config cfg4 --steps 1 --warmup 0 --no-cpu-baseline > $OUT/prof.log 2>&1 || { echo "rocprof rc=$?"; tail -5 $OUT/prof.log; exit 1; }
 find $OUT/prof -name "*kernel_stats.csv" | head -3
 for cfg in cfg3 cfg5; do
-  timeout -k 10 400 python -u bench.py --config $cfg --no-cpu-baseline > $OUT/$cfg.json 2> $OUT/$cfg.err || { echo "$cfg rc=$?"; tail -20 $OUT/$cfg.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --config $cfg --full --no-cpu-baseline > $OUT/$cfg.json 2> $OUT/$cfg.err || { echo "$cfg rc=$?"; tail -20 $OUT/$cfg.err; exit 1; }
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], '%.1f ms' % d['ms_per_step'], {k: round(v, 1) for k, v in d['stages_ms'].items()}, 'peak %.1f GB' % (d['counts']['peak_bytes'] / 1e9), 'parity', (d.get('parity') or {}).get('ok'))" $OUT/$cfg.json $cfg
 done

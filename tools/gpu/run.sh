@@ -13,6 +13,6 @@ if [ "$KEXPR" != "none" ]; then
   rc=$?; echo "pytest rc=$rc"; tail -3 $OUT/pytest_gpu.log
   if [ $rc -ne 0 ]; then grep -E "Error|assert|FAILED" $OUT/pytest_gpu.log | head -30; exit $rc; fi
 fi
-timeout -k 10 600 python -u bench.py $BARGS > $OUT/bench.log 2>&1
+timeout -k 10 600 python -u bench.py --full $BARGS > $OUT/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -1 $OUT/bench.log | cut -c1-3000
 exit $rc

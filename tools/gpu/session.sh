@@ -3,7 +3,8 @@
 # REBUILD=1 to rebuild on the box first): the -m gpu tests matching an optional -k expression, then
 # optional bench runs.  Every step has its own time limit; the first failure ends the session.
 # Usage: tools/gpu/session.sh <tag> [pytest -k expr | none] [bench args ... ]
-#        BENCH2="--config cfg5" adds a second bench line (its own log)
+#        BENCH2="--config cfg5 --full" adds a second bench line (its own log); --full among the bench
+#        args adds the host legs, the CPU baseline and the parity checks to a line
 cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=${1:-x}; KEXPR=${2:-}; shift 2 2>/dev/null; BARGS="$@"
 OUT=gpurun_out/$TAG; mkdir -p $OUT
