@@ -317,6 +317,30 @@ uint32_t mtg_dist_coresident(const uint64_t *ids, int world, int rank);
 int mtg_boss_write_dbg(const mtg_boss_chunk *chunk, const char *outbase, int graph_mode, int mask_dummy,
                        int64_t suffix_length, uint64_t *n_valid);
 
+/*
+ * The same files from a chunk in device memory, bit for bit what mtg_boss_write_dbg writes from the
+ * same arrays copied to the host.  `chunk` is any device chunk on the constructor's device: the
+ * descriptor mtg_boss_build_device[_dist] returned, or arrays the caller uploaded (W and last one byte
+ * per row, weights u32 per row or NULL).  The arrays are only read and stay valid; the call takes the
+ * constructor's mutex, runs on its stream and frees its device scratch before it returns.  The per-row
+ * stages (W's wavelet-tree bits, the rank words, the suffix-range index, the valid-edge mask, the
+ * weights' int_vector) run as kernels (csrc/dbg_device.hpp); the Huffman shape, the select supports,
+ * bit_vector_small and the framing stay host code.  <outbase>.dbg.weights is written when weights !=
+ * NULL and bits_per_count != 0.  mask_dummy: 0 or 1; 2 (pruning) returns MTG_ERR_UNSUPPORTED: copy the
+ * chunk to the host and use mtg_boss_write_dbg.  A row with W >= 16 returns MTG_ERR_ARGUMENT before any
+ * file is written.  graph_mode, suffix_length and *n_valid as for mtg_boss_write_dbg.
+ */
+typedef struct mtg_dbg_write_timings {
+    double device_ms;    /* kernels, events on the constructor's stream */
+    double d2h_ms;       /* payload copies to pinned host blocks */
+    double host_ms;      /* select supports, bit_vector_small, framing, file writes */
+    uint64_t d2h_bytes;
+} mtg_dbg_write_timings;
+int mtg_boss_write_dbg_device(mtg_boss_ctor *ctor, const mtg_boss_device_chunk *chunk,
+                              uint8_t bits_per_count, const char *outbase, int graph_mode,
+                              int mask_dummy, int64_t suffix_length, uint64_t *n_valid,
+                              mtg_dbg_write_timings *timings /* may be NULL */);
+
 /* One sdsl-lite container of the graph files written alone to `path` (the layout tests): kind 0
  * bit_vector_stat over `nbits` bits of `data`, 1 bit_vector_small (sd_vector or rrr_vector<63>,
  * whichever predict_size picks), 2 wt_huff<> over `nbits` bytes of `data`, 3 the sd_vector<> of the

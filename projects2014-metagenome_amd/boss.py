@@ -95,6 +95,15 @@ class Timings(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class DbgWriteTimings(ctypes.Structure):
+    """mtg_dbg_write_timings: where one write_dbg_device call spent its time."""
+    _fields_ = [("device_ms", ctypes.c_double), ("d2h_ms", ctypes.c_double), ("host_ms", ctypes.c_double),
+                ("d2h_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # exported C-ABI symbols (must match include/mtg_boss.h)
 EXPORTS = ("mtg_boss_abi_version", "mtg_last_error", "mtg_boss_ctor_create",
            "mtg_boss_ctor_destroy", "mtg_boss_ctor_get_k", "mtg_boss_ctor_add_sequences",
@@ -109,7 +118,7 @@ EXPORTS = ("mtg_boss_abi_version", "mtg_last_error", "mtg_boss_ctor_create",
            "mtg_boss_ctor_add_fasta", "mtg_device_copy", "mtg_kmc_load_device",
            "mtg_device_reads_free", "mtg_kmc_write_device", "mtg_host_pool_bytes",
            "mtg_host_pool_trim", "mtg_comm_create_callbacks", "mtg_comm_local_held_ms",
-           "mtg_boss_ctor_trim")
+           "mtg_boss_ctor_trim", "mtg_boss_write_dbg_device")
 
 COMM_ID_BYTES = 128
 
@@ -194,6 +203,9 @@ def lib():
                                            P(ctypes.c_uint64)]
         L.mtg_dbg_file_free.argtypes = [P(_DbgFile)]
         L.mtg_boss_ctor_trim.argtypes = [ctypes.c_void_p]
+        L.mtg_boss_write_dbg_device.argtypes = [ctypes.c_void_p, P(_DeviceChunk), ctypes.c_uint8,
+                                                ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                P(ctypes.c_uint64), P(DbgWriteTimings)]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -332,6 +344,7 @@ class BOSSChunkConstructor:
         self._k = k
         self._bits = bits_per_count
         self._canonical = canonical
+        self.last_dbg_timings = None  # the split of the last write_dbg_device call
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -440,6 +453,19 @@ class BOSSChunkConstructor:
                                                     d_read_starts, d_counts, n_reads, stream,
                                                     ctypes.byref(c)))
         return c
+
+    def write_dbg_device(self, chunk, outbase, canonical=False, mask_dummy=False, suffix_length=-1):
+        """Chunk.write_dbg from a chunk in device memory (mtg_boss_write_dbg_device): `chunk` is the
+        descriptor build_device returned or a _DeviceChunk over uploaded arrays.  The same bytes as
+        the host writer; the per-row stages run on the GPU.  Returns the valid edges after masking,
+        else rows - 1; last_dbg_timings holds the call's device / copy / host split."""
+        nv = ctypes.c_uint64(0)
+        t = DbgWriteTimings()
+        _check(lib().mtg_boss_write_dbg_device(self._h, ctypes.byref(chunk), self._bits or 0,
+                                               os.fsencode(outbase), int(bool(canonical)), int(mask_dummy),
+                                               int(suffix_length), ctypes.byref(nv), ctypes.byref(t)))
+        self.last_dbg_timings = t.as_dict()
+        return nv.value
 
     def timings(self):
         t = Timings()

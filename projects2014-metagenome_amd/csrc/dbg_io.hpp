@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <fstream>
 #include <queue>
@@ -344,13 +345,52 @@ inline uint64_t write_dbg(const std::string &base, const uint8_t *W, const uint6
                             bits_per_count);
 }
 
-// the files of one BOSS table (+ its valid-edge mask when `valid`)
-inline uint64_t write_dbg_arrays(const std::string &base, const uint8_t *W, const uint64_t *last, uint64_t n,
-                                 const uint64_t *F, uint64_t k, uint64_t mode, const std::vector<uint64_t> *valid,
-                                 int64_t suffix_length, const uint32_t *weights, unsigned bits_per_count) {
-    BossNav nav(W, last, n, F, k);
+// everything the three files hold besides F, k and the mode: the "compute payload" half fills it on the
+// host (compute_dbg_payload) or on the device (dbg_device.hpp), the "write from payload" half frames it
+struct DbgPayload {
+    uint64_t n = 0;
+    sdslio::WtHuffPayload wt;
+    const uint64_t *last = nullptr;        // packed, n bits
+    uint64_t last_ones = 0;
+    const uint64_t *last_rank = nullptr;   // rank_support_v5<1> words
+    uint64_t last_rank_words = 0;
+    uint64_t L = 0;                        // indexed suffix length (0 = no index)
+    const uint64_t *ranges = nullptr;      // 4^L pairs (first, last), the empty slots filled forward
+    uint64_t n_ranges = 0;
+    const uint64_t *valid = nullptr;       // packed valid-edge mask, or no .edgemask
+    uint64_t n_valid = 0;
+    const uint64_t *weights = nullptr;     // the width-w int_vector's words, or no .dbg.weights
+    unsigned weight_width = 0;
+    std::vector<uint64_t> last_rank_own, ranges_own, weights_own;
+};
+
+// the indexed suffix length write_dbg uses for a requested one
+inline uint64_t indexed_suffix_length(int64_t suffix_length, uint64_t k) {
     uint64_t L = suffix_length < 0 ? std::min<uint64_t>(10, k) : std::min<uint64_t>((uint64_t)suffix_length, k);
     if (L * 2 > 63) L = 0;  // "Node ranges for k-mer suffixes longer than ... cannot be indexed"
+    return L;
+}
+
+// boss.cpp:3153-3159: an empty slot takes the empty range after its predecessor
+inline void fill_empty_ranges(uint64_t *r, uint64_t count) {
+    for (uint64_t i = 1; i < count; ++i)
+        if (!r[2 * i + 1]) {
+            r[2 * i + 1] = r[2 * i - 1];
+            r[2 * i] = r[2 * i - 1] + 1;
+        }
+}
+
+// stage_ms (may be null): wall ms of [0] the wt_huff<> (its two select supports and bytes), [1] last (its
+// select support and bytes), [2] the rest of .dbg, [3] .edgemask (bit_vector_small), [4] .dbg.weights
+inline uint64_t write_dbg_payload(const std::string &base, const DbgPayload &p, const uint64_t *F, uint64_t k,
+                                  uint64_t mode, double *stage_ms = nullptr) {
+    auto t_prev = std::chrono::steady_clock::now();
+    auto lap = [&](int i) {
+        const auto t = std::chrono::steady_clock::now();
+        if (stage_ms) stage_ms[i] += std::chrono::duration<double, std::milli>(t - t_prev).count();
+        t_prev = t;
+    };
+    const uint64_t n = p.n;
     uint64_t n_valid = n ? n - 1 : 0;
     {
         std::ofstream o(base + ".dbg", std::ios::binary);
@@ -359,39 +399,74 @@ inline uint64_t write_dbg_arrays(const std::string &base, const uint8_t *W, cons
         for (int c = 0; c < 5; ++c) put_be(o, F[c]);
         put_be(o, k);
         put_be(o, kStateStat);
-        sdslio::put_wt_huff(o, W, n);
+        lap(2);
+        sdslio::write_wt_huff(o, p.wt);
+        lap(0);
         put_be(o, 4);  // logsigma of W: bits_per_char_W_
-        sdslio::put_bit_vector_stat(o, last, n);
+        sdslio::write_bit_vector_stat(o, p.last, n, p.last_ones, p.last_rank, p.last_rank_words);
+        lap(1);
         put_be(o, mode);
-        const auto ranges = index_suffix_ranges(nav, L);
-        put_be(o, L);
-        for (const auto &r : ranges) {
-            put_raw<uint64_t>(o, r.first);
-            put_raw<uint64_t>(o, r.second);
-        }
+        put_be(o, p.L);
+        o.write((const char *)p.ranges, (std::streamsize)(p.n_ranges * 16));
         if (!o.good()) throw std::runtime_error("Can't write to file " + base + ".dbg");
     }
-    if (valid) {
-        n_valid = 0;
-        for (uint64_t x : *valid) n_valid += __builtin_popcountll(x);
+    lap(2);
+    if (p.valid) {
+        n_valid = p.n_valid;
         std::ofstream o(base + ".edgemask", std::ios::binary);
-        sdslio::put_bit_vector_small(o, valid->data(), n);
+        sdslio::put_bit_vector_small(o, p.valid, n);
         if (!o.good()) throw std::runtime_error("Can't write to file " + base + ".edgemask");
     }
-    if (weights && bits_per_count) {  // the chunk's weights buffer renamed (node_weights.cpp:62-68)
+    lap(3);
+    if (p.weights) {  // the chunk's weights buffer renamed (node_weights.cpp:62-68)
+        std::ofstream o(base + ".dbg.weights", std::ios::binary);
+        sdslio::put_int_vector(o, p.weights, n * p.weight_width, (uint8_t)p.weight_width, false);
+        if (!o.good()) throw std::runtime_error("Can't write to file " + base + ".dbg.weights");
+    }
+    lap(4);
+    return n_valid;
+}
+
+// the files of one BOSS table (+ its valid-edge mask when `valid`)
+inline uint64_t write_dbg_arrays(const std::string &base, const uint8_t *W, const uint64_t *last, uint64_t n,
+                                 const uint64_t *F, uint64_t k, uint64_t mode, const std::vector<uint64_t> *valid,
+                                 int64_t suffix_length, const uint32_t *weights, unsigned bits_per_count) {
+    BossNav nav(W, last, n, F, k);
+    DbgPayload p;
+    p.n = n;
+    p.L = indexed_suffix_length(suffix_length, k);
+    sdslio::compute_wt_huff(W, n, &p.wt);
+    p.last = last;
+    for (uint64_t q = 0; q < (n + 63) / 64; ++q) p.last_ones += sdslio::popc(last[q]);
+    p.last_rank_own = sdslio::rank_v5_words(last, n);
+    p.last_rank = p.last_rank_own.data();
+    p.last_rank_words = p.last_rank_own.size();
+    const auto ranges = index_suffix_ranges(nav, p.L);
+    p.ranges_own.reserve(2 * ranges.size());
+    for (const auto &r : ranges) {
+        p.ranges_own.push_back(r.first);
+        p.ranges_own.push_back(r.second);
+    }
+    p.ranges = p.ranges_own.data();
+    p.n_ranges = ranges.size();
+    if (valid) {
+        p.valid = valid->data();
+        for (uint64_t x : *valid) p.n_valid += __builtin_popcountll(x);
+    }
+    if (weights && bits_per_count) {
         const unsigned w = bits_per_count;
-        std::vector<uint64_t> words((n * w + 63) / 64, 0);
+        std::vector<uint64_t> &words = p.weights_own;
+        words.assign((n * w + 63) / 64, 0);
         for (uint64_t i = 0; i < n; ++i) {
             const uint64_t v = (uint64_t)weights[i] & ((w >= 64) ? ~0ull : ((1ull << w) - 1));
             const uint64_t pos = i * w, q = pos >> 6, b = pos & 63;
             words[q] |= v << b;
             if (b + w > 64) words[q + 1] |= v >> (64 - b);
         }
-        std::ofstream o(base + ".dbg.weights", std::ios::binary);
-        sdslio::put_int_vector(o, words.data(), n * w, (uint8_t)w, false);
-        if (!o.good()) throw std::runtime_error("Can't write to file " + base + ".dbg.weights");
+        p.weights = words.data();
+        p.weight_width = w;
     }
-    return n_valid;
+    return write_dbg_payload(base, p, F, k, mode);
 }
 
 inline DbgFile read_dbg(const std::string &base) {

@@ -258,13 +258,20 @@ inline void skip_select_mcl(std::istream &in) {
 
 // bit_vector_stat::serialize (bit_vector_sdsl.hpp:267-281): the bit_vector, serialize_number(ones),
 // rank_support_v5<1>, select_support_mcl<1>, select_support_scan<0> (which writes nothing)
-inline void put_bit_vector_stat(std::ostream &o, const uint64_t *w, uint64_t nbits) {
+// the "write from payload" half: the words, their set bits and their rank_support_v5<1> words come from
+// the caller (computed on the host below, or on the device: dbg_device.hpp); the select support is host work
+inline void write_bit_vector_stat(std::ostream &o, const uint64_t *w, uint64_t nbits, uint64_t ones,
+                                  const uint64_t *rank5, uint64_t rank5_words) {
     put_bit_vector(o, w, nbits);
+    put_be(o, ones);
+    put_int_vector(o, rank5, 64 * rank5_words, 64, true);
+    put_select_mcl(o, w, nbits, true);
+}
+inline void put_bit_vector_stat(std::ostream &o, const uint64_t *w, uint64_t nbits) {
     uint64_t ones = 0;
     for (uint64_t q = 0; q < (nbits + 63) / 64; ++q) ones += popc(w[q]);
-    put_be(o, ones);
-    put_u64_vector(o, rank_v5_words(w, nbits));
-    put_select_mcl(o, w, nbits, true);
+    const std::vector<uint64_t> rank5 = rank_v5_words(w, nbits);
+    write_bit_vector_stat(o, w, nbits, ones, rank5.data(), rank5.size());
 }
 inline std::vector<uint64_t> get_bit_vector_stat(std::istream &in, uint64_t *nbits) {
     IntVec v = get_int_vector(in, 1);
@@ -378,24 +385,54 @@ inline HuffTree huff_shape(const uint64_t freq[256]) {
     return h;
 }
 
-inline void put_wt_huff(std::ostream &o, const uint8_t *W, uint64_t n) {
+// the payload of a wt_huff<>: the shape and the concatenated node bits with their rank_support_v<1>
+// words.  bv / rank point at the owned vectors (compute_wt_huff) or at blocks the device writer filled.
+struct WtHuffPayload {
+    uint64_t n = 0, sigma = 0, total = 0;
+    HuffTree tree;  // inner nodes carry their bv_pos_rank
+    const uint64_t *bv = nullptr;
+    const uint64_t *rank = nullptr;
+    uint64_t rank_words = 0;
+    std::vector<uint64_t> bv_own, rank_own;
+};
+
+// bits of all inner nodes of a shape
+inline uint64_t huff_total_bits(const HuffTree &h) {
+    uint64_t total = 0;
+    for (const auto &v : h.nodes)
+        if (v.child[0] != 0xFFFF) total += v.freq;
+    return total;
+}
+
+// ones before bit `pos` (<= nbits) from a bit vector and its rank_support_v<1> words
+inline uint64_t rank_v_query(const uint64_t *bv, const uint64_t *rank, uint64_t pos) {
+    const uint64_t q = pos >> 6, blk = q >> 3, i = q & 7;
+    uint64_t r = rank[2 * blk];
+    if (i) r += (rank[2 * blk + 1] >> (63 - 9 * i)) & 0x1FF;
+    if (pos & 63) r += popc(bv[q] & ((1ull << (pos & 63)) - 1));
+    return r;
+}
+
+// the "compute payload" half on the host: one descent per row
+inline void compute_wt_huff(const uint8_t *W, uint64_t n, WtHuffPayload *p) {
     uint64_t freq[256] = {0};
     for (uint64_t i = 0; i < n; ++i) ++freq[W[i]];
     uint64_t sigma = 0;
     for (int s = 0; s < 256; ++s) sigma += freq[s] != 0;
-    put_raw<uint64_t>(o, n);
-    put_raw<uint64_t>(o, sigma);
-    HuffTree h = huff_shape(freq);
-    uint64_t total = 0;
-    for (const auto &v : h.nodes)
-        if (v.child[0] != 0xFFFF) total += v.freq;
-    std::vector<uint64_t> bv((total + 63) / 64, 0);
+    p->n = n;
+    p->sigma = sigma;
+    p->tree = huff_shape(freq);
+    HuffTree &h = p->tree;
+    const uint64_t total = huff_total_bits(h);
+    p->total = total;
+    std::vector<uint64_t> &bv = p->bv_own;
+    bv.assign((total + 63) / 64, 0);
     std::vector<uint64_t> cur(h.nodes.size(), 0);
     for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t p = h.path[W[i]], len = p >> 56;
+        const uint64_t pth = h.path[W[i]], len = pth >> 56;
         uint16_t v = 0;
         for (uint64_t d = 0; d < len; ++d) {
-            const uint64_t b = (p >> d) & 1, pos = h.nodes[v].bv_pos + cur[v]++;
+            const uint64_t b = (pth >> d) & 1, pos = h.nodes[v].bv_pos + cur[v]++;
             if (b) bv[pos >> 6] |= 1ull << (pos & 63);
             v = h.nodes[v].child[b];
         }
@@ -408,10 +445,21 @@ inline void put_wt_huff(std::ostream &o, const uint8_t *W, uint64_t n) {
         if (v.bv_pos & 63) c += popc(bv[v.bv_pos >> 6] & ((1ull << (v.bv_pos & 63)) - 1));
         v.bv_pos_rank = c;
     }
-    put_bit_vector(o, bv.data(), total);
-    put_u64_vector(o, rank_v_words(bv.data(), total));
-    put_select_mcl(o, bv.data(), total, true);
-    put_select_mcl(o, bv.data(), total, false);
+    p->rank_own = rank_v_words(bv.data(), total);
+    p->bv = bv.data();
+    p->rank = p->rank_own.data();
+    p->rank_words = p->rank_own.size();
+}
+
+// the "write from payload" half; the two select supports are host work over the payload's bits
+inline void write_wt_huff(std::ostream &o, const WtHuffPayload &p) {
+    const HuffTree &h = p.tree;
+    put_raw<uint64_t>(o, p.n);
+    put_raw<uint64_t>(o, p.sigma);
+    put_bit_vector(o, p.bv, p.total);
+    put_int_vector(o, p.rank, 64 * p.rank_words, 64, true);
+    put_select_mcl(o, p.bv, p.total, true);
+    put_select_mcl(o, p.bv, p.total, false);
     put_raw<uint64_t>(o, (uint64_t)h.nodes.size());
     for (const auto &v : h.nodes) {
         put_raw<uint64_t>(o, v.bv_pos);
@@ -422,6 +470,12 @@ inline void put_wt_huff(std::ostream &o, const uint8_t *W, uint64_t n) {
     }
     o.write((const char *)h.leaf, sizeof(h.leaf));
     o.write((const char *)h.path, sizeof(h.path));
+}
+
+inline void put_wt_huff(std::ostream &o, const uint8_t *W, uint64_t n) {
+    WtHuffPayload p;
+    compute_wt_huff(W, n, &p);
+    write_wt_huff(o, p);
 }
 
 inline std::vector<uint8_t> get_wt_huff(std::istream &in) {

@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""From a device chunk to the graph files, two ways, at the bench's configs[1] workload.
+
+(a) the host writer: W / last / weights copied to the host, `last` packed, mtg_boss_write_dbg;
+(b) mtg_boss_write_dbg_device on the chunk where it lies, with its device / copy / host split.
+Each path runs once after one warm-up, both write --mask-dummy files with the default suffix index,
+and the two file sets are compared byte for byte.  Prints one JSON line and writes it to --out.
+Set MTG_TRACE=1 to get the host remainder of (b) by container on stderr."""
+import argparse
+import filecmp
+import importlib
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=10_000_000)
+    ap.add_argument("--read-len", type=int, default=150)
+    ap.add_argument("--k", type=int, default=31, help="DBG k (BOSS k = k - 1)")
+    ap.add_argument("--count-width", type=int, default=0)
+    ap.add_argument("--dir", default=None, help="where the files go (default: a fresh directory on /dev/shm or $TMPDIR)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dbg_device_bench.json"))
+    args = ap.parse_args()
+
+    import torch
+    import bench
+    boss = importlib.import_module("projects2014-metagenome_amd.boss")
+    if not torch.cuda.is_available():
+        sys.exit("dbg_device_bench: no GPU (a measurement does not fall back)")
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    seq = bench.make_reads_device(torch, args.reads, args.read_len, 1000, "genome", 10.0, device)
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    kb = args.k - 1
+    ctor = boss.IBOSSChunkConstructor.initialize(kb, both_strands=True, bits_per_count=args.count_width)
+    dc = ctor.build_device(seq.data_ptr(), seq.numel())
+    build_ms = ctor.timings().total_ms
+    n = int(dc.n)
+
+    parent = args.dir or ("/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir())
+    out_dir = tempfile.mkdtemp(prefix="mtg_dbg_bench_", dir=parent)
+    L = boss.lib()
+
+    def host_path(base):
+        t0 = time.perf_counter()
+        W = np.empty(n, np.uint8)
+        last = np.empty(n, np.uint8)
+        assert L.mtg_memcpy_d2h(W.ctypes.data, dc.W, n) == 0
+        assert L.mtg_memcpy_d2h(last.ctypes.data, dc.last, n) == 0
+        weights = None
+        if args.count_width:
+            weights = np.empty(n, np.uint32)
+            assert L.mtg_memcpy_d2h(weights.ctypes.data, dc.weights, 4 * n) == 0
+        t1 = time.perf_counter()
+        ch = boss.Chunk(kb, W, None, np.array(list(dc.F), np.uint64), weights, bits_per_count=args.count_width,
+                        last_words=boss.pack_last(last))
+        t2 = time.perf_counter()
+        nv = ch.write_dbg(base, canonical=True, mask_dummy=True)
+        t3 = time.perf_counter()
+        return nv, {"d2h_s": t1 - t0, "pack_last_s": t2 - t1, "write_dbg_s": t3 - t2, "total_s": t3 - t0,
+                    "d2h_bytes": n * (2 + (4 if args.count_width else 0))}
+
+    def device_path(base):
+        t0 = time.perf_counter()
+        nv = ctor.write_dbg_device(dc, base, canonical=True, mask_dummy=True)
+        t1 = time.perf_counter()
+        split = dict(ctor.last_dbg_timings)
+        split["total_s"] = t1 - t0
+        return nv, split
+
+    try:
+        host_path(os.path.join(out_dir, "warm_h"))
+        device_path(os.path.join(out_dir, "warm_d"))
+        nv_h, host = host_path(os.path.join(out_dir, "h"))
+        nv_d, dev = device_path(os.path.join(out_dir, "d"))
+        same, sizes = True, {}
+        for ext in (".dbg", ".edgemask", ".dbg.weights"):
+            h, d = os.path.join(out_dir, "h" + ext), os.path.join(out_dir, "d" + ext)
+            if os.path.exists(h) != os.path.exists(d):
+                same = False
+            elif os.path.exists(h):
+                sizes[ext] = os.path.getsize(h)
+                same = same and filecmp.cmp(h, d, shallow=False)
+    finally:
+        shutil.rmtree(out_dir, ignore_errors=True)
+    res = {
+        "workload": "configs[1] generator: %d reads of %d bp, DBG k = %d, canonical, count width %d"
+                    % (args.reads, args.read_len, args.k, args.count_width),
+        "gpu": torch.cuda.get_device_name(0),
+        "rows": n, "build_device_ms": build_ms, "directory": parent, "file_bytes": sizes,
+        "protocol": "each path once after one warm-up; wall clock around calls that end synchronised",
+        "host_writer": host, "device_writer": dev,
+        "ratio_host_over_device": host["total_s"] / dev["total_s"],
+        "n_valid": int(nv_d), "n_valid_equal": bool(nv_h == nv_d), "bytes_equal": bool(same),
+    }
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if same and nv_h == nv_d else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
