@@ -457,7 +457,7 @@ __global__ __launch_bounds__(256) void rc_map_kernel(const Key<L> *__restrict__ 
     }
 }
 
-// rc_map_kernel over a canonical set left in its speculative buckets (Ctx::gap in boss_pipeline.hip):
+// rc_map_kernel over a canonical set left in its speculative buckets (BuildState::gap in ctx.hpp):
 // bucket g's keys keys[bstart[g] ..) map to rc_out[ustart[g] .. ustart[g + 1]), one wave per bucket,
 // 4 loads in flight per lane
 template <int L>
@@ -496,7 +496,7 @@ __global__ __launch_bounds__(256) void rc_map_gapped_kernel(const Key<L> *__rest
 
 /*
  * K4 fused with the rc sort's first MSD level (odd K, the canonical set in its speculative buckets,
- * Ctx::gap): the rc keys go straight into their level-1 buckets -- one cursor reservation per (tile,
+ * BuildState::gap): the rc keys go straight into their level-1 buckets -- one cursor reservation per (tile,
  * bucket), the tile ranked by bucket in LDS and written as runs, as msd_partition_kernel does -- instead
  * of being written in canonical order by rc_map_gapped_kernel and partitioned by a second pass (its
  * histogram pass, rc_map_gapped_kernel with no output, gives the bucket starts).  A tile is TILE

@@ -18,6 +18,7 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <sys/types.h>
@@ -38,1705 +39,14 @@
 #include "kmc.hpp"
 #include "msd_sort.hpp"
 #include "radix_sort.hpp"
+#include "ctx.hpp"
+#include "sort_unique.hpp"
 
 namespace mtg {
 
 static thread_local std::string g_last_error;
 
 static void set_error(const std::string &msg) { g_last_error = msg; }
-
-#define HIP_CHECK(x)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (x);                                                                \
-        if (e_ != hipSuccess)                                                               \
-            throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(e_) +    \
-                                     " at " #x);                                            \
-    } while (0)
-
-// growable device buffers, reused across builds
-class Workspace {
-  public:
-    enum Slot {
-        SEQ, STARTS, RCOUNTS, KA, KB, CA, CB, SUMS, DESC, HIST, STARTS_DIGIT, SMALL, BUCKETS,
-        FLAGS, DA, DB, STREAM, SCOUNT, OW, OLAST, OWEIGHTS, MSD_COUNTS, MSD_BSTART,
-        MSD_CURSOR, MSD_GSTART, MSD_UCOUNT, MSD_USTART, MSD_OVF, MSD_GLIST, FB_K, FB_V, RC_ALT, RC_ALTC, REAL, REALC, SPLITS, DTCNT, DTOFF, INFLAG, HIST1, HIST_ROWS,
-        // multi-GPU build: exchange buffers, routing and the query join
-        XA, XAC, XB, XBC, XHIST, XSTART_A, XSTART_B, XMAT, BOUNDS, RTCNT, RTOFF, XGATHER, QSEND, QRECV,
-        QFLAG, QTCNT, QTOFF, DSRC, DSEND, DRECV, RUN_IDX, RUN_DELTA, RUN_OFF, KMC_LUT, KMC_REC, DUP_TABLE, FUSED_HIST, FUSED_CUR, STRIPE_CUR,
-        LAST_BITS, DPOS, DWL, RANGE_BINS, MSD_GBUCKET, RC_CSTART, RC_COMB, RC_SENDC, PACKED, W4, FA_RAW, FA_TLAST, FA_PREV, FA_TA, FA_TB, FA_OA, FA_OB, FA_KOFF, RID_AT, BRUNS,
-        SK_OWN, SK_TCNT, SK_TOFF, SK_WORDS, SK_LENS, SK_CNT, SK_RWORDS, SK_RLENS, SK_RCNT, SK_NW, SK_WOFF, SK_SEQ,
-        SK_STARTS, SK_RID, CANON_IDX, SPEC_A, SPEC_B, SPEC_CAP, SPEC_CUR, GAP_BSTART, GAP_USTART, CANON, CANONC,
-        FUSED_SEL, WN, SPEC_AC, SPEC_BC, SPEC1_CAPS, SPEC1_START, SPEC1_TV, QINDEX, DBITMAP, RC_L1START, RC_L1CUR, RC_TILEG,
-        KA2, ROUND_DELTA, XA2, XAC2, CA2, SPEC_MID_TV, NSLOTS
-    };
-    ~Workspace() {
-        // every device block once, by its base (a slot or kept entry may be a piece of one: carve)
-        for (auto &r : roots_)
-            if (r.base) (void)hipFree(r.base);
-    }
-    void *get(Slot s, size_t bytes, size_t keep = 0, hipStream_t stream = nullptr) {
-        Buf &b = bufs_[s];
-        bytes = std::max<size_t>(bytes, 256);
-        if (b.cap < bytes) {
-            size_t cap = 0;
-            int root = -1;
-            void *p = take_cached(bytes, &cap, &root);
-            if (!p) {
-                cap = bytes + std::min<size_t>(bytes / 8, 1ull << 30);
-                const auto t0 = std::chrono::steady_clock::now();
-                bool dropped = false, carved = false;
-                if (carve_always) {
-                    p = take_cached(bytes, &cap, &root, true);
-                    carved = p != nullptr;
-                }
-                if (!p && !try_malloc(&p, cap, &root)) {
-                    // no room for a new block: a piece carved off a kept block that holds the request (the
-                    // rest stays kept: the later stages of a batched build fit in the blocks its rounds gave
-                    // back instead of each taking a whole one), and only then kept blocks freed one at a
-                    // time, largest first (freeing kept blocks is what costs: ~12 ms per GB while the driver
-                    // clears them, 2.3 s a build at configs[2] when every failed allocation dropped the
-                    // whole cache).  MTG_WS_CARVE=1 (tests): carve before any new block
-                    p = take_cached(bytes, &cap, &root, true);
-                    carved = p != nullptr;
-                    while (!p && !cache_.empty() && drop_largest()) {
-                        dropped = true;
-                        cap = bytes + std::min<size_t>(bytes / 8, 1ull << 30);
-                        if (!try_malloc(&p, cap, &root)) p = nullptr;
-                    }
-                    if (!p && !try_malloc(&p, cap, &root)) {
-                        size_t fr = 0, tot = 0;
-                        (void)hipMemGetInfo(&fr, &tot);
-                        throw std::runtime_error("HIP error out of memory: workspace slot " + std::to_string((int)s) +
-                                                 " wants " + std::to_string(cap >> 20) + " MiB (held " +
-                                                 std::to_string(held() >> 20) + " MiB in all slots, this one " +
-                                                 std::to_string(b.cap >> 20) + " MiB; free " + std::to_string(fr >> 20) +
-                                                 " MiB)");
-                    }
-                }
-                if (carved) ++carves_;
-                if (trace && cap >= (1ull << 28))
-                    fprintf(stderr, "[mtg trace] workspace slot %d: %s %lu MiB%s, %.1f ms (held %lu MiB, kept %lu MiB)\n",
-                            (int)s, carved ? "carved" : "new", (unsigned long)(cap >> 20),
-                            dropped ? " after dropping the kept blocks" : "",
-                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
-                            (unsigned long)(held() >> 20), (unsigned long)(cached() >> 20));
-            }
-            if (keep && b.ptr) HIP_CHECK(hipMemcpyAsync(p, b.ptr, keep, hipMemcpyDeviceToDevice, stream));
-            if (b.ptr) {
-                HIP_CHECK(hipDeviceSynchronize());
-                give_back(b);
-            }
-            b.ptr = p;
-            b.cap = cap;
-            b.root = root;
-            ++gen_[s];
-        }
-        return b.ptr;
-    }
-    void swap(Slot a, Slot b) {
-        std::swap(bufs_[a], bufs_[b]);
-        ++gen_[a], ++gen_[b];
-    }
-    // the buffers a build's sort, rc, dummy and emit stages hold (not its input, look-back descriptors
-    // or pass-A histograms): a build in rounds frees the previous build's before sizing its rounds
-    void release_stage_buffers(bool keep_outputs = false) {
-        // keep_outputs (mtg_boss_ctor_trim): the last build's device chunk arrays (W, last, weights) stay
-        for (Slot sl : {KA, KB, CA, CB, SUMS, BUCKETS, FLAGS, DA, DB, STREAM, SCOUNT, OW, OLAST, OWEIGHTS, FB_K, FB_V,
-                        RC_ALT, RC_ALTC, REAL, REALC, INFLAG, XA, XAC, XB, XBC, QSEND, QRECV, QFLAG, DSRC, DSEND,
-                        DRECV, RC_SENDC, LAST_BITS, W4, WN, DPOS, DWL, CANON, CANONC, CANON_IDX, SPEC_A, SPEC_B,
-                        SPEC_AC, SPEC_BC, KA2, XA2, XAC2, CA2})
-            if (!keep_outputs || (sl != OW && sl != OLAST && sl != OWEIGHTS)) release(sl);
-    }
-    // a slot gives its buffer back (batched builds drop their round buffers before the later stages
-    // grow).  The block is kept for the next get() of about its size rather than freed: freeing and
-    // mapping again the ~200 GB of a configs[3] share cost seconds per build while the driver clears
-    // the pages (and slowed the kernels running meanwhile).  A hipMalloc that fails frees the kept
-    // blocks and tries again.
-    void release(Slot s) {
-        Buf &b = bufs_[s];
-        if (b.ptr) {
-            HIP_CHECK(hipDeviceSynchronize());
-            give_back(b);
-        }
-        b.ptr = nullptr;
-        b.cap = 0;
-        b.root = -1;
-        ++gen_[s];
-    }
-    // every byte the workspace holds, in slots and kept blocks
-    uint64_t held() const {
-        uint64_t t = cached();
-        for (const auto &b : bufs_) t += b.cap;
-        return t;
-    }
-    uint64_t cached() const {
-        uint64_t t = 0;
-        for (const auto &b : cache_) t += b.cap;
-        return t;
-    }
-    // free HBM for new buffers: the device's free memory plus the kept blocks
-    uint64_t free_bytes() const {
-        size_t fr = 0, tot = 0;
-        HIP_CHECK(hipMemGetInfo(&fr, &tot));
-        return (uint64_t)fr + cached();
-    }
-    // the largest kept whole block freed (a block partly carved out to a slot stays); false: none
-    bool drop_largest() {
-        size_t big = cache_.size();
-        for (size_t i = 0; i < cache_.size(); ++i)
-            if (whole(cache_[i]) && (big == cache_.size() || cache_[i].cap > cache_[big].cap)) big = i;
-        if (big == cache_.size()) return false;
-        HIP_CHECK(hipDeviceSynchronize());
-        free_root(cache_[big].root);
-        cache_.erase(cache_.begin() + (long)big);
-        return true;
-    }
-    void drop_cache() {
-        if (cache_.empty()) return;
-        HIP_CHECK(hipDeviceSynchronize());
-        std::vector<Buf> keep;
-        for (auto &b : cache_) {
-            if (whole(b)) free_root(b.root);
-            else keep.push_back(b);
-        }
-        cache_.swap(keep);
-    }
-    // end of a build: free the kept blocks no get() took during it (released in an earlier build and
-    // idle since), so a big build's blocks do not pin HBM for the life of the constructor; the blocks
-    // this build gave back stay for the next build of the same shape
-    void end_build() {
-        bool any = false;
-        for (const auto &b : cache_) any |= b.age > 0 && whole(b);
-        if (any) {
-            HIP_CHECK(hipDeviceSynchronize());
-            std::vector<Buf> keep;
-            for (auto &b : cache_) {
-                if (b.age > 0 && whole(b)) free_root(b.root);
-                else keep.push_back(b);
-            }
-            cache_.swap(keep);
-        }
-        for (auto &b : cache_) b.age = 1;
-    }
-    uint64_t held_slot(Slot s) const { return bufs_[s].cap; }
-    uint64_t carves() const { return carves_; }
-    bool carve_always = false;  // MTG_WS_CARVE=1
-    const void *peek(Slot s) const { return bufs_[s].ptr; }
-    // bumped whenever the slot's buffer changes (regrown or released): a block given back may be
-    // handed to another slot, so a pointer comparison alone cannot tell that the data is still there
-    uint64_t generation(Slot s) const { return gen_[s]; }
-
-  private:
-    struct Buf {
-        void *ptr = nullptr;
-        size_t cap = 0;
-        uint32_t age = 0;  // kept blocks: builds ended since it was given back (end_build)
-        int root = -1;     // the device block (roots_) it is, or is a piece of
-    };
-    struct Root {
-        void *base = nullptr;  // hipMalloc'ed, hipFree'd once when no piece of it is in use
-        size_t cap = 0;
-    };
-    bool whole(const Buf &b) const { return b.root >= 0 && b.ptr == roots_[b.root].base && b.cap == roots_[b.root].cap; }
-    bool try_malloc(void **p, size_t cap, int *root) {
-        if (hipMalloc(p, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        size_t i = 0;
-        while (i < roots_.size() && roots_[i].base) ++i;
-        if (i == roots_.size()) roots_.emplace_back();
-        roots_[i] = Root{*p, cap};
-        *root = (int)i;
-        return true;
-    }
-    void free_root(int r) {
-        (void)hipFree(roots_[r].base);
-        roots_[r] = Root{};
-    }
-    // a slot's buffer back to the kept list, merged with the kept pieces of its block next to it (a
-    // block whose pieces are all back is whole again: the next build of the same shape takes it whole)
-    void give_back(Buf b) {
-        b.age = 0;
-        for (bool merged = true; merged;) {
-            merged = false;
-            for (size_t i = 0; i < cache_.size(); ++i) {
-                Buf &o = cache_[i];
-                if (o.root != b.root || b.root < 0) continue;
-                if ((char *)o.ptr + o.cap == (char *)b.ptr) {
-                    b.ptr = o.ptr, b.cap += o.cap;
-                } else if ((char *)b.ptr + b.cap == (char *)o.ptr) {
-                    b.cap += o.cap;
-                } else {
-                    continue;
-                }
-                cache_.erase(cache_.begin() + (long)i);
-                merged = true;
-                break;
-            }
-        }
-        cache_.push_back(b);
-    }
-    // the smallest kept block of at least `bytes` and at most about twice that (a far bigger block
-    // stays for the request it was made for); carve (the device has no room left): the smallest kept
-    // block or piece that holds `bytes`, its front handed out and its rest kept when that is 256 MiB+
-    void *take_cached(size_t bytes, size_t *cap, int *root, bool carve = false) {
-        size_t best = cache_.size();
-        for (size_t i = 0; i < cache_.size(); ++i)
-            if (cache_[i].cap >= bytes && (carve || cache_[i].cap <= 2 * bytes + (64u << 20)) &&
-                (best == cache_.size() || cache_[i].cap < cache_[best].cap))
-                best = i;
-        if (best == cache_.size()) return nullptr;
-        Buf &k = cache_[best];
-        void *p = k.ptr;
-        *root = k.root;
-        const size_t piece = (bytes + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);  // 2 MiB aligned
-        if (carve && k.cap >= piece + (256u << 20)) {
-            *cap = piece;
-            k.ptr = (char *)k.ptr + piece;
-            k.cap -= piece;
-            k.age = 0;
-            return p;
-        }
-        *cap = k.cap;
-        cache_.erase(cache_.begin() + (long)best);
-        return p;
-    }
-    Buf bufs_[NSLOTS];
-    uint64_t gen_[NSLOTS] = {};
-    std::vector<Root> roots_;
-    uint64_t carves_ = 0;
-
-  public:
-    bool trace = false;  // MTG_TRACE: report every fresh allocation of 256 MiB or more
-
-  private:
-    std::vector<Buf> cache_;
-};
-
-struct Small {  // one device word block, zeroed per use
-    unsigned long long total;
-    unsigned long long totals[2];
-    unsigned long long fhist[8];
-    uint32_t counter;
-    uint32_t skip;
-    uint32_t root_same;
-    uint32_t bad_dummy;
-    uint32_t bruns;  // bucket_index: listed long runs
-    uint32_t fasta_bad;  // fasta_split_kernel: a '+' sequence line
-    uint32_t gidx_bad;   // group_gather_kernel: the output bucket index was abandoned
-    uint32_t spec_ovf;   // msd_partition_kernel: a speculative bucket overflowed
-    uint32_t wbad;       // window_reads_kernel: the input is not one window per read
-    unsigned long long wcursor;  // window_reads_kernel: keys written
-    uint32_t error;
-};
-
-class EventTimer {
-  public:
-    explicit EventTimer(hipStream_t s) : s_(s) {}
-    ~EventTimer() {
-        for (auto e : evs_) (void)hipEventDestroy(e);
-    }
-    int mark() {
-        hipEvent_t e;
-        HIP_CHECK(hipEventCreate(&e));
-        HIP_CHECK(hipEventRecord(e, s_));
-        evs_.push_back(e);
-        return (int)evs_.size() - 1;
-    }
-    double ms(int a, int b) {
-        float t = 0;
-        HIP_CHECK(hipEventElapsedTime(&t, evs_[a], evs_[b]));
-        return t;
-    }
-
-  private:
-    hipStream_t s_;
-    std::vector<hipEvent_t> evs_;
-};
-
-struct Ctx {
-    Workspace ws;
-    hipStream_t stream = nullptr;
-    Small *small = nullptr;
-    mtg_boss_timings timings{};
-    uint32_t epoch = 0;           // look-back granule epoch of the last launch
-    size_t desc_words = 0;        // zeroed capacity of the descriptor buffer
-    // accumulated over the onesweep launches of the real-k-mer sorts of one build
-    double radix_ms = 0, radix_bytes = 0;
-    uint64_t radix_launches = 0;
-    bool track_partition = false;  // time the msd_partition launches of the real-k-mer sorts
-    bool use_lsd = false;          // MTG_SORT=lsd: LSD onesweep + unique instead of MSD (the fallback
-                                   // sort of overflowing groups, selectable for the parity tests)
-    bool emit_slow = false;        // MTG_EMIT=slow: always the compacting emit kernel (the redundant-sink path)
-    bool debug = false;            // MTG_DEBUG=1: host-side checks between stages
-    bool trace = false;            // MTG_TRACE=1: per-step wall times and sizes of the dist build
-    bool fused = true;             // MTG_FUSED=0: K1 writes in window order, K2 partitions after
-    uint64_t fused_min = 1ull << 22;  // MTG_FUSED_MIN: fewest window starts for the fused K1
-    uint32_t force_ranges = 0;     // MTG_RANGES=P: collect in P key ranges (tests; else planned from memory)
-    double mem_budget = 0;         // memory_preallocated (bytes; 0 = free HBM)
-    bool disk = false;             // MTG_CONTAINER_VECTOR_DISK: the bounded-memory (range-batched) build
-    bool host_output = false;      // the build's arrays go to the host (build_chunk): it may spill
-    bool force_spill = false;      // MTG_SPILL=1: spill whenever the build runs in key ranges (tests)
-    std::string swap_dir;          // spill files of the disk container (swap_dir of initialize)
-    uint64_t disk_cap = 0;         // at most this many bytes of spill files (disk_cap_bytes); the rest in RAM
-    std::vector<uint8_t> spill_W, spill_last;  // the spilled build's output rows (host)
-    std::vector<uint32_t> spill_weights;
-    uint64_t spilled_bytes = 0;    // bytes the last build kept outside HBM
-    uint32_t hist_rows = 2048;     // MTG_HIST_ROWS: workgroups of the fused K1 histogram pass (tests
-                                   // lower it so the grid-stride + prefetch loop runs on small inputs)
-    double fused_ms = 0;           // device time of the last fused extract+partition launch
-    bool fused_emit = true;        // MTG_FUSED_EMIT=0: K7 writes the lifted stream, K8 reads it (the
-                                   // redundant-sink path)
-    bool routed_min = false;       // MTG_ROUTED_CANON=min: the routed collect keeps min(fwd, rc)
-    int dist_collect = 1;          // MTG_DIST_COLLECT: 1 routed keys (default), 0 super-k-mers
-                                   // (=superkmer), 2 local collect + exchange of sorted runs (=local)
-    unsigned fused_b1 = 0;         // MTG_FUSED_B1=n: the fused K1's level-1 digit forced to n bits (A/B runs)
-    bool wide_b1 = true;           // MTG_WIDE_B1=0: no 10-bit level 1 (fused_plan)
-    bool lu_fast = true;           // MTG_LU_FAST=0: local_unique_kernel's per-key list positions (A/B)
-    bool fast2_ppt8 = true;        // MTG_FAST2_PPT8=0: the u128 packed-word pass B at 16 windows a thread (256 threads)
-    bool rc_wide = true;           // MTG_RC_WIDE=0: the u128 rc sort planned like the unique (half-full merge groups)
-    bool lu_wpe2 = true;           // MTG_LU_WPE2=0: the u128 local unique compiled for 1 wave per SIMD (no VGPR cap)
-    bool fast2 = true;             // MTG_FAST2=0: the u128 rounds' pass B as the generic extract_partition_kernel
-    int canon_mode = 1;            // the single-build extraction's canonical representative (cmode); the
-                                   // super-k-mer owners of a multi-GPU build extract with 2
-    uint32_t merge_it = 1;         // MTG_MERGE_IT: local_merge_kernel's least outputs per thread (A/B)
-    bool range_scan = false;       // MTG_COLLECT=ranges: a build too big for one pass collects in key ranges
-    bool kmc_mirror = true;  // add_kmc copies the first database to the device while reading it
-                                   // that re-scan the reads (both strands) even where the canonical
-                                   // rounds of the fused K1 apply (collect_rounds_fused)
-    bool kspec = true;             // MTG_KSPEC=0: the fused K1 passes with K a runtime argument at K = 31 too
-    bool dist_pull = true;         // MTG_DIST_SINKS=query: the multi-GPU sink join by routed queries
-                                   // (target_split + query_join) instead of the pulled edge slices
-    bool rc_fuse = true;           // MTG_RC_FUSE=0: the rc keys of a gapped canonical set written in canonical
-                                   // order and partitioned by the rc sort's own level 1, not straight into
-                                   // its level-1 buckets (rc_partition_gapped_kernel)
-    bool dummy_bitmap = false;     // MTG_DUMMY_BITMAP=1: the source levels with few real chars as bits of a
-                                   // bitmap (dummy_write_kernel) -- the sort gains 0.25 ms, the write pass
-                                   // loses as much, so off by default
-    bool dummy_ranks = true;       // MTG_DUMMY_SORT=lifted: sort the dummies as lifted keys, not as
-                                   // dense u64 ranks (dummy_encode_kernel)
-    // bucket index of the last msd_sort_unique's output over its final bucket bits, when every group
-    // was one bucket (its group starts are that index): the fused rc merge reuses it for the canonical keys
-    struct GroupIndex {
-        const void *keys = nullptr;
-        uint64_t n = 0;
-        unsigned bits = 0, nbits = 0;
-        const uint64_t *start = nullptr;
-    } gidx;
-    bool want_gidx = false;  // the next msd_sort_unique's output feeds the fused rc merge
-    // a batched collect round's share of the canonical set's bucket index (collect_rounds_fused): the
-    // speculative final level's gather writes entries [lo, hi) of `start` (2^bits buckets) as positions
-    // + off in the whole set, and says so in `written`
-    struct RoundIndex {
-        uint64_t *start = nullptr;
-        unsigned bits = 0;
-        uint64_t off = 0, lo = 0, hi = 0;
-        bool written = false;
-    } ridx;
-    bool round_index = true;  // MTG_ROUND_INDEX=0: the canonical set's index by a bucket_index pass
-    // where the next msd_sort_unique's final gather writes its compact distinct keys (and counts) instead of
-    // *keys (the exchange pieces append each piece's keys in place: routed_pieces); *keys then points there
-    void *sort_out = nullptr;
-    uint32_t *sort_out_vals = nullptr;
-    uint64_t sort_out_cap = ~0ull;  // keys sort_out holds (more distinct keys: the usual gather into *keys)
-    // the single build's canonical set left in the speculative level's bucket layout (no
-    // group_gather_kernel): bucket g's keys at keys[bstart[g] ..), compact at ustart[g] ..
-    // (ustart[g + 1] - ustart[g] keys).  rc_map and the fused rc merge read it there;
-    // ensure_compact() writes the compact array to dst when anything else needs it.
-    struct GappedSet {
-        bool valid = false;
-        const void *keys = nullptr;
-        void *dst = nullptr;
-        uint64_t u = 0, nb = 0;
-        const uint64_t *bstart = nullptr, *ustart = nullptr;
-    } gap;
-    bool defer_gather_req = false;  // set around the single build's canonical collect
-    bool defer_gather = true;       // MTG_DEFER_GATHER=0: the speculative level always gathers
-    bool spec_rc = true;            // MTG_SPEC_RC=0: the rc sort's final level exact (tests the fallbacks)
-    unsigned min_levels = 0;        // MTG_MSD_LEVELS=n: plan at least n MSD levels (tests the 3-level path)
-    // MTG_SPEC3=0: the speculative final level only for 2-level plans.  (Sampled every 8th tile, the
-    // level-3 buckets of level-2 buckets only a few tiles long were sized badly: at 20 M reads every
-    // step overflowed into the exact level, sort 30.3 -> 38.9 ms; level 3 now samples every tile's
-    // first eighth.)
-    bool spec3 = true;
-    // the speculative final level's local unique writes over its own buckets (each group is read whole
-    // before it writes): one slack-sized buffer instead of two.  MTG_SPEC_INPLACE=0: two
-    bool spec_inplace = true;
-    // a free buffer the speculative final level of a 3-level sort may partition into (the batched
-    // collect's level-1 array, sized for it, free once level 2 has moved the keys out): no third block
-    void *spec_into = nullptr;
-    uint64_t spec_into_bytes = 0;
-    // a collect round whose keys are sparse in the plan's final buckets (it spans more level-1 buckets
-    // than its share: canonical k-mers crowd the small prefixes) takes one final bit fewer, so its local
-    // unique runs fuller groups (configs[3]'s second round: 2.95 M groups of ~390 distinct keys, 25.7 vs
-    // 20.6 ms for the first round's 1.25 M).  MTG_ROUND_BITS=0: the plan's bits in every round
-    bool round_bits = true;
-    bool rounds_one_b = true;  // two collect rounds share one pass B (collect_rounds_fused); MTG_ROUNDS_ONE_B=0: not
-    // MTG_DIST_PIECES=n: the routed multi-GPU collect sends exchange 1 in n pieces on the exchange stream,
-    // each sorted by its owner while the next one is in flight (routed_pieces); 1 = one exchange, then the sort
-    uint32_t dist_pieces = 4;
-    bool dist_pieces_set = false;  // MTG_DIST_PIECES given: exactly that many (else fewer for small shares)
-    hipStream_t xstream = nullptr;  // the multi-GPU exchange stream (created by the first distributed build)
-    bool spec_final = true;  // MTG_SPEC=0: the exact final MSD level (histogram pass) instead of the
-                             // sample-sized one (spec_final_level)
-    bool spec_tiny = false;  // MTG_SPEC_CAPS=tiny: speculative buckets without slack (tests force the
-                             // overflow fallback with it)
-    bool spec_lu_fail = false;  // MTG_SPEC_LU_FAIL=1: the speculative level's local unique pass reports an
-                                // overflow after it ran (tests the exact level after that late fallback)
-    // MTG_SPEC_L1=0: the exact fused pass A (a histogram of every window) instead of the sampled one
-    // and the speculative level-1 layout (fused_pass_b_spec), used from MTG_SPEC_L1_MIN windows on;
-    // MTG_SPEC_L1_SAMPLE: pass A counts every n-th tile
-    bool spec_l1 = true;
-    bool spec_l1_tiny = false;  // MTG_SPEC_L1_CAPS=tiny: segments without slack (tests force its fallback)
-    uint64_t spec_l1_min = 1ull << 28;
-    uint32_t spec_l1_sample = 8;
-    uint32_t spec_l1_stripes = 16;  // MTG_SPEC_L1_STRIPES: segments per level-1 bucket (a power of two <= 256)
-    uint32_t spec_l1_slack = 16;    // MTG_SPEC_L1_SLACK: segment slack 1/n of the estimate (+ 3 sigma + 1024)
-    // the speculative level-1 layout of the last fused K1 until the level-2 pass has read it: gap1_n
-    // positions, tile t of the level-2 tiling holding keys in its first gap1_tv[t] positions
-    uint64_t gap1_n = 0;
-    const uint32_t *gap1_tv = nullptr;
-    // the previous-level buckets a padded input's keys occupy, [gap1_lo, gap1_hi) (spec_mid_level; 0 / 0:
-    // unknown, every bucket)
-    uint64_t gap1_lo = 0, gap1_hi = 0;
-    // a 3-level sort's speculative middle level (spec_mid_level) partitions into this buffer (the batched
-    // collect's KB, sized for it); MTG_SPEC_MID=0: the exact middle level
-    void *spec_mid_into = nullptr;
-    uint64_t spec_mid_bytes = 0;
-    bool spec_mid = true;
-    // bucket index over the real edges, built by the dummy stage and reused by the split emit
-    const void *bidx_keys = nullptr;
-    uint64_t bidx_n = 0;
-    const uint64_t *bidx = nullptr;
-    unsigned bidx_shift = 0;
-    uint64_t bidx_gen = 0;  // the BUCKETS slot's generation when the index was written
-};
-
-static inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
-
-// the extraction kernels' canonical argument: 0 basic, 1 min(fwd, rc), 2 the strand whose top 12 bits hash
-// smaller (boss_kernels.hpp: take_rc) -- any one representative per {x, rc x} gives the same real edges and
-// weights; 2 spreads the representatives over the key space (the multi-GPU collects, Ctx::canon_mode)
-static inline int cmode(const Ctx &c, bool canonical) { return canonical ? c.canon_mode : 0; }
-
-// The few environment switches, read once per constructor.  All but MTG_DEBUG / MTG_TRACE select
-// alternate device paths that exist for correctness (fallbacks the parity tests force on small
-// inputs), never a faster configuration.
-static void load_knobs(Ctx &c) {
-    auto is = [](const char *name, const char *val) {
-        const char *e = getenv(name);
-        return e && std::string(e) == val;
-    };
-    c.use_lsd = is("MTG_SORT", "lsd");
-    c.emit_slow = is("MTG_EMIT", "slow");
-    c.fused = !is("MTG_FUSED", "0");
-    c.fused_emit = !is("MTG_FUSED_EMIT", "0");
-    c.dummy_ranks = !is("MTG_DUMMY_SORT", "lifted");
-    c.range_scan = is("MTG_COLLECT", "ranges");
-    c.wide_b1 = !is("MTG_WIDE_B1", "0");
-    c.kmc_mirror = !is("MTG_KMC_MIRROR", "0");
-    c.lu_fast = !is("MTG_LU_FAST", "0");
-    c.lu_wpe2 = !is("MTG_LU_WPE2", "0");
-    c.rc_wide = !is("MTG_RC_WIDE", "0");
-    c.fast2_ppt8 = !is("MTG_FAST2_PPT8", "0");
-    c.fast2 = !is("MTG_FAST2", "0");
-    if (const char *e = getenv("MTG_MERGE_IT")) c.merge_it = (uint32_t)std::max(1L, std::min(64L, atol(e)));
-    if (const char *v = getenv("MTG_FUSED_B1")) c.fused_b1 = (unsigned)std::min(10, std::max(0, atoi(v)));
-    c.spec_final = !is("MTG_SPEC", "0");
-    c.defer_gather = !is("MTG_DEFER_GATHER", "0");
-    c.spec_rc = !is("MTG_SPEC_RC", "0");
-    c.spec3 = !is("MTG_SPEC3", "0");
-    c.rounds_one_b = !is("MTG_ROUNDS_ONE_B", "0");
-    c.ws.carve_always = is("MTG_WS_CARVE", "1");
-    c.spec_inplace = !is("MTG_SPEC_INPLACE", "0");
-    c.round_bits = !is("MTG_ROUND_BITS", "0");
-    c.round_index = !is("MTG_ROUND_INDEX", "0");
-    c.spec_mid = !is("MTG_SPEC_MID", "0");
-    if (const char *e = getenv("MTG_DIST_PIECES")) {
-        c.dist_pieces = (uint32_t)std::max(1L, std::min(16L, atol(e)));
-        c.dist_pieces_set = true;
-    }
-    c.spec_tiny = is("MTG_SPEC_CAPS", "tiny");
-    c.spec_lu_fail = is("MTG_SPEC_LU_FAIL", "1");
-    c.spec_l1 = !is("MTG_SPEC_L1", "0");
-    c.dist_pull = !is("MTG_DIST_SINKS", "query");
-    c.kspec = !is("MTG_KSPEC", "0");
-    c.dummy_bitmap = is("MTG_DUMMY_BITMAP", "1");
-    c.rc_fuse = !is("MTG_RC_FUSE", "0");
-    c.spec_l1_tiny = is("MTG_SPEC_L1_CAPS", "tiny");
-    if (const char *e = getenv("MTG_SPEC_L1_STRIPES")) {
-        const long v = atol(e);
-        if (v >= 1 && v <= 256 && (v & (v - 1)) == 0) c.spec_l1_stripes = (uint32_t)v;
-    }
-    if (const char *e = getenv("MTG_SPEC_L1_SLACK")) c.spec_l1_slack = (uint32_t)std::max(2L, std::min(1024L, atol(e)));
-    if (const char *e = getenv("MTG_SPEC_L1_MIN")) c.spec_l1_min = strtoull(e, nullptr, 10);
-    if (const char *e = getenv("MTG_SPEC_L1_SAMPLE")) c.spec_l1_sample = (uint32_t)std::max(1L, std::min(64L, atol(e)));
-    if (const char *v = getenv("MTG_MSD_LEVELS")) c.min_levels = (unsigned)std::min(3, std::max(0, atoi(v)));
-    c.dist_collect = is("MTG_DIST_COLLECT", "superkmer") ? 0 : is("MTG_DIST_COLLECT", "local") ? 2 : 1;
-    c.routed_min = is("MTG_ROUTED_CANON", "min");
-    c.force_spill = is("MTG_SPILL", "1");
-    c.debug = getenv("MTG_DEBUG") != nullptr;
-    c.trace = getenv("MTG_TRACE") != nullptr;
-    c.ws.trace = c.trace;
-    if (const char *e = getenv("MTG_FUSED_MIN")) c.fused_min = strtoull(e, nullptr, 10);
-    if (const char *e = getenv("MTG_RANGES")) c.force_ranges = (uint32_t)std::max(0L, std::min(4096L, atol(e)));
-    if (const char *e = getenv("MTG_HIST_ROWS")) c.hist_rows = (uint32_t)std::max(1L, std::min(2048L, atol(e)));
-}
-
-// zero the per-stage words; the error word is sticky for the whole build (checked at the end)
-static void reset_small(Ctx &c) {
-    HIP_CHECK(hipMemsetAsync(c.small, 0, offsetof(Small, error), c.stream));
-}
-
-static uint64_t read_u64(Ctx &c, const unsigned long long *p) {
-    unsigned long long v = 0;
-    HIP_CHECK(hipMemcpyAsync(&v, p, sizeof(v), hipMemcpyDeviceToHost, c.stream));
-    HIP_CHECK(hipStreamSynchronize(c.stream));
-    return v;
-}
-
-// MTG_TRACE: host wall time since the previous trace point (stream drained first)
-struct Tracer {
-    Ctx &c;
-    int rank;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void operator()(const char *what, uint64_t a = 0, uint64_t b = 0) {
-        if (!c.trace) return;
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[mtg trace r%d] %-22s %9.3f ms  %lu %lu\n", rank, what,
-                std::chrono::duration<double, std::milli>(now - t).count(), (unsigned long)a, (unsigned long)b);
-        t = now;
-    }
-};
-
-static void check_error_word(Ctx &c) {
-    uint32_t e = 0;
-    HIP_CHECK(hipMemcpyAsync(&e, &c.small->error, sizeof(e), hipMemcpyDeviceToHost, c.stream));
-    HIP_CHECK(hipStreamSynchronize(c.stream));
-    if (e & 1u) throw std::runtime_error("device look-back timed out (error word " + std::to_string(e) + ")");
-    if (e) throw std::runtime_error("device partition counts disagree with the histogram pass (error word " +
-                                    std::to_string(e) + ")");
-}
-
-// Descriptor array for one look-back launch plus its epoch.  Granules of older epochs read as
-// "not ready", so the array is zeroed only when it grows or the 16-bit epoch wraps.
-static uint64_t *acquire_desc(Ctx &c, uint64_t words, uint32_t *epoch) {
-    uint64_t *d = (uint64_t *)c.ws.get(Workspace::DESC, words * 8);
-    if (words > c.desc_words || c.epoch >= 0xFFFF) {
-        size_t cap = std::max<size_t>(words, c.desc_words);
-        d = (uint64_t *)c.ws.get(Workspace::DESC, cap * 8);
-        HIP_CHECK(hipMemsetAsync(d, 0, cap * 8, c.stream));
-        c.desc_words = cap;
-        c.epoch = 0;
-    }
-    *epoch = ++c.epoch;
-    return d;
-}
-
-// bucket index of a sorted key array (boss_kernels.hpp: bucket_index_kernel + the grid-wide fill of
-// its long empty runs)
-constexpr uint32_t kBucketRuns = 4096;
-template <int L>
-static void bucket_index(Ctx &c, const Key<L> *keys, uint64_t n, unsigned shift, uint64_t nb, uint64_t *start) {
-    uint64_t *runs = (uint64_t *)c.ws.get(Workspace::BRUNS, kBucketRuns * 24);
-    HIP_CHECK(hipMemsetAsync(&c.small->bruns, 0, 4, c.stream));
-    const uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(n + 1, 256), 8192));
-    bucket_index_kernel<L><<<dim3((unsigned)g), dim3(256), 0, c.stream>>>(keys, n, shift, nb, start, runs,
-                                                                         &c.small->bruns, kBucketRuns);
-    HIP_CHECK(hipGetLastError());
-    bucket_fill_kernel<<<dim3(1024), dim3(256), 0, c.stream>>>(runs, &c.small->bruns, kBucketRuns, start);
-    HIP_CHECK(hipGetLastError());
-}
-
-// exclusive scans of the per-pass digit counts: block p scans hist[p * 256 ..] into start[p * 256 ..]
-__global__ __launch_bounds__(256) void digit_starts_kernel(const unsigned long long *__restrict__ hist,
-                                                           uint64_t *__restrict__ start) {
-    __shared__ uint64_t s_wsum[4];
-    const uint32_t t = threadIdx.x, p = blockIdx.x;
-    const uint64_t v = hist[p * 256 + t];
-    uint64_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = __shfl_up(x, o, 64);
-        if ((t & 63) >= (uint32_t)o) x += y;
-    }
-    if ((t & 63) == 63) s_wsum[t >> 6] = x;
-    __syncthreads();
-    uint64_t before = 0;
-    for (uint32_t w = 0; w < (t >> 6); ++w) before += s_wsum[w];
-    start[p * 256 + t] = before + x - v;
-}
-
-// LSD radix sort of keys[0..n) (and vals) over the low nbits; result left in *keys / *vals
-// (pointers swapped with *alt / *valt as passes ping-pong).  Passes whose digit is the same for every key
-// are skipped.  spec_first: the lowest pass is launched before the histogram reaches the host (the digit
-// starts are scanned on the device), so the copy and the host's look at it overlap that pass -- for
-// inputs whose lowest digit is never constant (the dense dummy ranks); a constant one costs one pass.
-template <int L, bool HAS_VAL>
-static void radix_sort(Ctx &c, Key<L> **keys, Key<L> **alt, uint32_t **vals, uint32_t **valt,
-                       uint64_t n, unsigned nbits, bool stats, bool spec_first = false) {
-    if (n < 2) return;
-    const int passes = (int)ceil_div(nbits, 8);
-    auto *hist = (unsigned long long *)c.ws.get(Workspace::HIST, passes * 256 * 8);
-    HIP_CHECK(hipMemsetAsync(hist, 0, passes * 256 * 8, c.stream));
-    const uint64_t hgrid = std::min<uint64_t>(ceil_div(n, 256), 4096);
-    radix_histogram_kernel<L><<<dim3((unsigned)hgrid), dim3(256), 0, c.stream>>>(*keys, n, passes, hist);
-    HIP_CHECK(hipGetLastError());
-    auto *dstart = (uint64_t *)c.ws.get(Workspace::STARTS_DIGIT, passes * 256 * 8);
-    digit_starts_kernel<<<dim3((unsigned)passes), dim3(256), 0, c.stream>>>(hist, dstart);
-    HIP_CHECK(hipGetLastError());
-    std::vector<unsigned long long> h(passes * 256);
-    HIP_CHECK(hipMemcpyAsync(h.data(), hist, h.size() * 8, hipMemcpyDeviceToHost, c.stream));
-    constexpr int TILE = SortTraits<L>::TILE;
-    const uint64_t tiles = ceil_div(n, TILE);
-    if (tiles > 0xFFFFFFFFull) throw std::runtime_error("sort too large");
-    EventTimer tm(c.stream);
-    std::vector<int> done;
-    auto launch = [&](int p) {
-        uint32_t epoch;
-        uint64_t *desc = acquire_desc(c, tiles * 256, &epoch);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        tm.mark();
-        onesweep_kernel<L, HAS_VAL><<<dim3((unsigned)tiles), dim3(SortTraits<L>::BLOCK), 0, c.stream>>>(
-            *keys, *alt, HAS_VAL ? *vals : nullptr, HAS_VAL ? *valt : nullptr, n, 8u * p,
-            dstart + p * 256, desc, epoch, &c.small->counter, &c.small->error);
-        HIP_CHECK(hipGetLastError());
-        tm.mark();
-        std::swap(*keys, *alt);
-        if (HAS_VAL) std::swap(*vals, *valt);
-        done.push_back(p);
-    };
-    if (spec_first) launch(0);
-    HIP_CHECK(hipStreamSynchronize(c.stream));  // the histogram on the host (`h` is a local)
-    for (int p = spec_first ? 1 : 0; p < passes; ++p) {
-        bool trivial = false;
-        for (int d = 0; d < 256; ++d)
-            if (h[p * 256 + d] == n) trivial = true;
-        if (!trivial) launch(p);
-    }
-    if (stats && !done.empty()) {
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        for (size_t i = 0; i < done.size(); ++i) c.radix_ms += tm.ms(2 * i, 2 * i + 1);
-        c.radix_launches += done.size();
-        c.radix_bytes += (double)done.size() * 2.0 * n * (sizeof(Key<L>) + (HAS_VAL ? 4 : 0));
-    }
-}
-
-__global__ void set_u64_kernel(uint64_t *p, uint64_t a) { *p = a; }
-
-// p[i] = v for i in [lo, hi)
-__global__ __launch_bounds__(256) void fill_u64_kernel(uint64_t *__restrict__ p, uint64_t lo, uint64_t hi, uint64_t v) {
-    const uint64_t T = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = lo + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += T) p[i] = v;
-}
-
-__global__ void set_pair_kernel(uint64_t *p, uint64_t a, uint64_t b) {
-    p[0] = a;
-    p[1] = b;
-}
-
-// Duplication estimate for the MSD plan: m evenly spaced sample keys go into a hash table of
-// 64-bit fingerprints; the number of samples that find their fingerprint already present is
-// C ~ m^2 / (2 n) * E_w[mult] (E_w: multiplicity seen by a random occurrence).  Reads arrive in
-// random genome order, so evenly spaced samples are as good as random ones.
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    return x ^ (x >> 33);
-}
-
-template <int L>
-__global__ void dup_sample_kernel(const Key<L> *__restrict__ keys, uint64_t n, uint32_t m,
-                                  unsigned long long *__restrict__ table, uint32_t mask,
-                                  unsigned long long *__restrict__ hits) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= m) return;
-    const Key<L> k = keys[(uint64_t)((double)j * ((double)n / m))];
-    uint64_t h = 0x9e3779b97f4a7c15ull;
-#pragma unroll
-    for (int i = 0; i < L; ++i) h = mix64(h ^ k.w[i]);
-    h |= 1;  // 0 marks an empty slot
-    uint32_t slot = (uint32_t)(h >> 32) & mask;
-    while (true) {
-        const unsigned long long prev = atomicCAS(&table[slot], 0ull, (unsigned long long)h);
-        if (prev == 0) return;
-        if (prev == h) {
-            atomicAdd(hits, 1ull);
-            return;
-        }
-        slot = (slot + 1) & mask;
-    }
-}
-
-// expected copies per distinct key of keys[0..n), conservative (it may err low, which costs a
-// planned bit, never an overflowing plan); `fallback` below the sampling size
-template <int L>
-static double estimate_dup(Ctx &c, const Key<L> *keys, uint64_t n, double fallback) {
-    constexpr uint32_t M = 1u << 20, SLOTS = 1u << 22;
-    if (n < 8ull * M) return fallback;
-    unsigned long long *table = (unsigned long long *)c.ws.get(Workspace::DUP_TABLE, (SLOTS + 1) * 8ull);
-    HIP_CHECK(hipMemsetAsync(table, 0, (SLOTS + 1) * 8ull, c.stream));
-    dup_sample_kernel<L><<<dim3(M / 256), dim3(256), 0, c.stream>>>(keys, n, M, table, SLOTS - 1, table + SLOTS);
-    HIP_CHECK(hipGetLastError());
-    const double hits = (double)read_u64(c, table + SLOTS);
-    const double ew = 2.0 * (double)n * hits / ((double)M * M);  // E_w[multiplicity]
-    const double dup = std::max(1.0, ew / 1.2);  // E_w / mean: 1.17 at 10x, 1.29 at 1.25x
-    if (c.debug) fprintf(stderr, "[mtg debug] dup estimate n=%lu hits=%.0f E_w=%.2f -> %.2f\n", (unsigned long)n, hits, ew, dup);
-    return dup;
-}
-
-// Sort + unique (+ saturating count merge) of keys[0..n) over their low nbits by MSD
-// partitioning and per-group LDS hashing (msd_sort.hpp).  `dup` is the expected number of
-// copies per distinct key, used only to plan the partition depth; a wrong guess costs time,
-// never correctness (overflowing groups take another level or the LSD fallback).
-// Result: sorted distinct keys in *keys (counts in *vals); returns their number.
-struct MsdPlan {
-    unsigned levels;
-    unsigned digit_end[4];  // cumulative significant bits after each level
-};
-
-// partition depth: enough top bits T that an average final bucket holds <= LIMIT/3 distinct
-// keys (canonical k-mers are up to 2x denser at small prefixes), in levels of <= max_digit
-// bits (one full read + scatter each)
-constexpr double kPlanDiv = 2.5;  // planned distinct keys per final bucket = LIMIT / kPlanDiv
-
-template <int L>
-static MsdPlan msd_plan(const Ctx &c, uint64_t n, unsigned nbits, double dup) {
-    const double LIMIT = (double)LocalTraits<L>::LIMIT / 2;  // half-size LDS tables
-    const unsigned dmax = MSD_DBITS;
-    unsigned T = 0;
-    while (T < nbits && T < 3 * dmax && (double)n / dup / (double)(1ull << T) > LIMIT / kPlanDiv)
-        ++T;
-    MsdPlan p{};
-    p.levels = (T + dmax - 1) / dmax;
-    if (c.min_levels > p.levels && T >= c.min_levels) p.levels = c.min_levels;  // (tests: MTG_MSD_LEVELS)
-    for (unsigned l = 1; l <= p.levels; ++l) p.digit_end[l] = T * l / p.levels;
-    return p;
-}
-
-static void note_bucket_index(Ctx &c, const void *keys, uint64_t n, const uint64_t *start, unsigned shift);
-
-// The plan of the rc sort fused with the merge (and of the canonical set's bucket index it reads): u128 keys
-// take one final bit fewer than the unique's plan, so a merge group holds ~480 rc + ~480 canonical keys in
-// its 1024-key LDS arrays instead of ~240 + 240 -- the per-group cost (barriers, table setup) then spreads
-// over twice the keys (configs[2]: 2.03e9 rc keys over 2^22 buckets, not 2^23)
-template <int L>
-static MsdPlan rc_plan(const Ctx &c, uint64_t n, unsigned nbits) {
-    return msd_plan<L>(c, L == 2 && c.rc_wide ? std::max<uint64_t>(1, n / 2) : n, nbits, 1.0);
-}
-
-// the rc sort's local pass fused with the merge into the real edges (local_merge_kernel)
-template <int L>
-struct RcMerge {
-    const Key<L> *ck;   // the sorted canonical set
-    const uint32_t *cv;
-    uint64_t nc;
-    Key<L> *out;        // the real edges: merge(canonical, sorted rc)
-    uint32_t *outc;
-    bool done = false;  // set when the fused pass ran (else the caller merges)
-    uint64_t *istart = nullptr;  // also the dummy stage's bucket index over the top ib bits of out
-    unsigned ib = 0;
-};
-
-// bucket capacities of the speculative final level: the sampled count scaled up, 20 % + 512 keys
-// of slack (a bucket of ~4600 keys overflows with probability ~1e-10 at a 1/8 sample)
-// (buckets outside [blo, bhi) -- below the input's first or above its last previous-level prefix --
-// hold no key and get no slack: a round of a batched collect fills a fraction of the buckets)
-// align (a speculative middle level): capacities rounded up to whole tiles of the next level's tiling
-__global__ void spec_caps_kernel(const uint32_t *__restrict__ sample, uint64_t nb, uint32_t stride,
-                                 uint32_t *__restrict__ cap, bool tiny, uint64_t blo, uint64_t bhi,
-                                 uint32_t align = 0) {
-    const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
-    if (b < blo || b >= bhi) {
-        cap[b] = 0;
-        return;
-    }
-    uint32_t v = tiny ? (uint32_t)(((uint64_t)sample[b] * stride) / 2)
-                      : (uint32_t)(((uint64_t)sample[b] * stride * 6) / 5) + 512u;
-    if (align) v = (v + align - 1) / align * align;
-    cap[b] = v;
-}
-
-// the tile fill of a speculative middle level's output (tile-aligned buckets [bstart[b], bstart[b + 1]),
-// keys up to cur[b]): tile t holds keys in its first tv[t] positions -- the padded-input convention of
-// the next level's kernels (Ctx::gap1_tv)
-__global__ void spec_tile_fill_kernel(const uint64_t *__restrict__ bstart, const unsigned long long *__restrict__ cur,
-                                      uint64_t nb, uint32_t tile, uint32_t *__restrict__ tv) {
-    const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
-    const uint64_t s = bstart[b], e = bstart[b + 1], k = cur[b];
-    for (uint64_t t = s / tile; t < e / tile; ++t) {
-        const uint64_t t0 = t * tile;
-        tv[t] = (uint32_t)(k <= t0 ? 0 : min<uint64_t>(tile, k - t0));
-    }
-}
-
-// The final MSD level of the main sort (level 2 after the fused K1's level 1) without its exact
-// histogram pass (msd_hist_kernel reads all N keys: 1.68 ms at configs[1]): the buckets are sized
-// from a histogram of every 8th tile with slack, the partition writes into them (a reservation past
-// a bucket's end is refused and flagged), and every bucket is one local_unique group whose keys end
-// where its cursor stopped.  Returns the distinct count with the sorted keys in *keys, or ~0 when
-// it does not apply (too little free HBM for the two slack-sized buffers) or a bucket or a group
-// overflowed -- then nothing the caller needs was touched and it runs the exact level.
-// spec_counts_kernel: the keys each speculative bucket received (its cursor minus its start)
-__global__ void spec_counts_kernel(const uint64_t *__restrict__ bstart, const unsigned long long *__restrict__ cur,
-                                   uint64_t nb, uint32_t *__restrict__ cnt) {
-    const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < nb) cnt[b] = (uint32_t)(cur[b] - bstart[b]);
-}
-
-// one workgroup per bucket over buckets [lo, hi), in launches of at most 2^22 workgroups (a grid holds
-// fewer than 2^32 work-items: 2^23 buckets of 512 threads do not launch at once)
-template <typename F>
-static void bucket_pieces(uint64_t lo, uint64_t hi, F &&launch) {
-    constexpr uint64_t CH = 1ull << 22;
-    for (uint64_t g0 = lo; g0 < hi; g0 += CH) launch(g0, (unsigned)std::min(CH, hi - g0));
-}
-
-// the deferred gather of a canonical set left in bucket layout (Ctx::gap), for a consumer that reads
-// it compact
-static void ensure_compact(Ctx &c) {
-    if (!c.gap.valid) return;
-    c.gap.valid = false;
-    if (!c.gap.nb) return;
-    bucket_pieces(0, c.gap.nb, [&](uint64_t g0, unsigned cnt) {
-        group_gather_kernel<1, false><<<dim3(cnt), dim3(256), 0, c.stream>>>(
-            (const Key<1> *)c.gap.keys, nullptr, c.gap.bstart, c.gap.ustart, (Key<1> *)c.gap.dst, nullptr, nullptr, 0,
-            nullptr, nullptr, g0);
-        HIP_CHECK(hipGetLastError());
-    });
-}
-
-// rm (the rc sort fused with the merge, distinct input): the same buckets go to local_merge_kernel,
-// one bucket per group, each group's output after the canonical keys before its bucket (cidx, the
-// canonical sort's bucket index) and the rc keys the buckets before it received.
-template <int L, bool COUNTED>
-static uint64_t spec_final_level(Ctx &c, Key<L> **keys, uint32_t **vals, uint64_t n, unsigned nbits, unsigned bp,
-                                 unsigned bb, uint32_t cmax, bool distinct, RcMerge<L> *rm,
-                                 const Ctx::GroupIndex &cidx, bool fine = false, Key<L> *spare = nullptr) {
-    // spare (c.spec_into, uncounted): a free buffer of c.spec_into_bytes the buckets may take instead of SPEC_A
-    // COUNTED: the counts travel with their keys (SPEC_AC / SPEC_BC) and add with saturation in the
-    // local pass, as in the exact level (configs[4]'s counted route)
-    if constexpr (L != 1) {
-        return ~0ull;
-    } else {
-        constexpr double KB = COUNTED ? 12.0 : 8.0;  // bytes of a key and its count
-        if (distinct != (rm != nullptr)) return ~0ull;  // the plain unique, or the fused rc merge
-        if (rm && !c.spec_rc) return ~0ull;
-        if (rm && !(cidx.keys == (const void *)rm->ck && cidx.n == rm->nc && cidx.bits == bb && cidx.nbits == nbits &&
-                    bb <= 32 && (!rm->istart || rm->ib >= bb)))
-            return ~0ull;
-        constexpr uint32_t SS = 8;
-        constexpr int TILE = MsdTraits<L>::TILE;
-        // after a speculative level-1 layout the input is the padded array (Ctx::gap1_n)
-        const bool g1 = bp && c.gap1_n && !rm;
-        const uint64_t npos = g1 ? c.gap1_n : n;
-        const uint32_t *tv = g1 ? c.gap1_tv : nullptr;
-        const uint64_t tiles = ceil_div(npos, TILE);
-        if (c.use_lsd || !c.spec_final || tiles < 64 * SS || bb - bp > 9 || bb > 24) return ~0ull;
-        // a padded input samples every tile: its tiles' fills differ (segment tails, empty tiles), so a
-        // tile-granular sample sized the buckets badly (overflow at 2 M reads)
-        if (g1) fine = true;
-        const uint64_t nb = 1ull << bb;
-        // the deferred gather (the fused rc merge follows) leaves the distinct keys in their own buckets
-        // (SPEC_B); otherwise the local unique writes over its input buckets (in place: one buffer)
-        const bool gap_out = !COUNTED && c.defer_gather_req && c.defer_gather && c.want_gidx;
-        const bool inplace = !rm && c.spec_inplace && !gap_out;
-        if (COUNTED) spare = nullptr;
-        // the slack-sized buffers must fit next to everything else
-        if (!spare) {
-            const uint64_t fr = c.ws.free_bytes();
-            if ((double)n * KB * 1.4 * (inplace ? 1.0 : 2.0) > 0.5 * (double)fr + (double)c.ws.held_slot(Workspace::SPEC_A) +
-                                                  (double)c.ws.held_slot(Workspace::SPEC_B) +
-                                                  (double)c.ws.held_slot(Workspace::SPEC_AC) +
-                                                  (double)c.ws.held_slot(Workspace::SPEC_BC))
-                return ~0ull;
-        }
-        uint32_t *h = (uint32_t *)c.ws.get(Workspace::MSD_COUNTS, nb * 4);
-        HIP_CHECK(hipMemsetAsync(h, 0, nb * 4, c.stream));
-        // 2 levels: every 8th tile (level-1 buckets span hundreds of tiles); 3 levels: the first 1/8 of every
-        // tile (level-2 buckets can be only a few tiles long, and a tile-granular sample missed them)
-        constexpr uint32_t GT = 8;  // fine sample: tiles per workgroup (one LDS window flush)
-        msd_hist_kernel<L><<<dim3((unsigned)(fine ? ceil_div(tiles, GT) : ceil_div(tiles, SS))), dim3(MSD_BLOCK), 0,
-                             c.stream>>>(*keys, npos, nbits, bb, bp, h, fine ? 1 : SS, fine ? SS : 1, fine ? GT : 1, tv);
-        HIP_CHECK(hipGetLastError());
-        // the buckets the keys can occupy: those under the previous level's first and last prefix
-        // (a padded input's ends are not keys: every bucket)
-        uint64_t blo = 0, bhi = nb;
-        if (g1 && c.gap1_hi > c.gap1_lo) {  // a speculative middle level's output: its key range is known
-            blo = c.gap1_lo << (bb - bp);
-            bhi = std::min<uint64_t>(nb, c.gap1_hi << (bb - bp));
-        } else if (bp && !g1) {
-            Key<L> ends[2];
-            HIP_CHECK(hipMemcpyAsync(&ends[0], *keys, sizeof(Key<L>), hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipMemcpyAsync(&ends[1], *keys + (n - 1), sizeof(Key<L>), hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));
-            blo = (ends[0].w[0] >> (nbits - bp)) << (bb - bp);
-            bhi = std::min<uint64_t>(nb, ((ends[1].w[0] >> (nbits - bp)) + 1) << (bb - bp));
-        }
-        uint32_t *cap = (uint32_t *)c.ws.get(Workspace::SPEC_CAP, nb * 4);
-        spec_caps_kernel<<<dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, c.stream>>>(h, nb, SS, cap, c.spec_tiny,
-                                                                                        blo, bhi);
-        HIP_CHECK(hipGetLastError());
-        uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::MSD_BSTART, (nb + 1) * 8);
-        {
-            uint32_t ep;
-            const uint64_t st = ceil_div(nb, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(cap, nb, bstart, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-        }
-        const uint64_t C = read_u64(c, (const unsigned long long *)(bstart + nb));
-        if (spare && C * sizeof(Key<L>) > c.spec_into_bytes) spare = nullptr;
-        if (!spare) {  // the capacity is known now: both slack-sized buffers (one: fused rc merge, in place) must fit
-            const uint64_t fr = c.ws.free_bytes();
-            const double need = (double)C * KB * (rm || inplace ? 1.0 : 2.0);
-            const double have = 0.9 * (double)fr + (double)c.ws.held_slot(Workspace::SPEC_A) +
-                                (double)c.ws.held_slot(Workspace::SPEC_AC) +
-                                (rm ? 0.0 : (double)c.ws.held_slot(Workspace::SPEC_B) +
-                                                (double)c.ws.held_slot(Workspace::SPEC_BC));
-            if (need > have) {
-                if (c.debug) fprintf(stderr, "[mtg debug] speculative level: capacity %lu does not fit, exact level\n",
-                                     (unsigned long)C);
-                return ~0ull;
-            }
-        }
-        Key<L> *sa = spare ? spare : (Key<L> *)c.ws.get(Workspace::SPEC_A, C * sizeof(Key<L>));
-        uint32_t *sac = COUNTED ? (uint32_t *)c.ws.get(Workspace::SPEC_AC, C * 4) : nullptr;
-        auto *cur = (unsigned long long *)c.ws.get(Workspace::SPEC_CUR, nb * 8);
-        HIP_CHECK(hipMemcpyAsync(cur, bstart, nb * 8, hipMemcpyDeviceToDevice, c.stream));
-        HIP_CHECK(hipMemsetAsync(&c.small->spec_ovf, 0, 4, c.stream));
-        EventTimer tm(c.stream);
-        tm.mark();
-        msd_partition_kernel<L, COUNTED><<<dim3((unsigned)xcd_grid(tiles)), dim3(MSD_BLOCK), 0, c.stream>>>(
-            *keys, sa, COUNTED ? *vals : nullptr, sac, npos, nbits, bb, bp, cur, 1,
-            (const unsigned long long *)(bstart + 1), &c.small->spec_ovf, tv);
-        HIP_CHECK(hipGetLastError());
-        tm.mark();
-        uint32_t povf = 0;
-        HIP_CHECK(hipMemcpyAsync(&povf, &c.small->spec_ovf, 4, hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        if (c.track_partition && c.radix_launches == 0) {
-            c.radix_ms += tm.ms(0, 1);
-            c.radix_launches += 1;
-            c.radix_bytes += 2.0 * n * KB;
-        }
-        if (povf) {
-            if (c.debug) fprintf(stderr, "[mtg debug] speculative level: a bucket overflowed, exact level\n");
-            c.radix_ms = 0, c.radix_launches = 0, c.radix_bytes = 0;
-            ++c.timings.spec_fallbacks;
-            return ~0ull;
-        }
-        // g1: the padded input stays marked (Ctx::gap1_n) until this level succeeds -- a local pass that
-        // overflows below returns ~0 and the caller's exact level must read the padded array again
-        auto consumed_gap1 = [&]() {
-            if (g1) c.gap1_n = 0, c.gap1_tv = nullptr, c.gap1_lo = c.gap1_hi = 0;  // the buckets below are compact per bucket
-        };
-        if (rm) {  // the fused rc merge over the speculative buckets
-            uint32_t *cnt = (uint32_t *)c.ws.get(Workspace::SPEC_CAP, nb * 4);
-            spec_counts_kernel<<<dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, c.stream>>>(bstart, cur, nb, cnt);
-            HIP_CHECK(hipGetLastError());
-            uint64_t *gbase = (uint64_t *)c.ws.get(Workspace::MSD_USTART, (nb + 1) * 8);
-            {
-                uint32_t ep;
-                const uint64_t st = ceil_div(nb, 4096);
-                uint64_t *desc = acquire_desc(c, st, &ep);
-                HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-                scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(cnt, nb, gbase, desc, ep,
-                                                                                  &c.small->counter, &c.small->error);
-                HIP_CHECK(hipGetLastError());
-            }
-            constexpr int CAP = MergeLocalTraits<L>::CAP;
-            uint32_t *olist = (uint32_t *)c.ws.get(Workspace::MSD_OVF, nb * 4);  // the overflowing groups
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            uint64_t *istart = rm->istart;
-            // the canonical keys where they are: compact, or still in their own bucket layout (c.gap,
-            // whose compact index is cidx.start)
-            const bool gapped = c.gap.valid && c.gap.dst == (const void *)rm->ck;
-            const Key<L> *ck = gapped ? (const Key<L> *)c.gap.keys : rm->ck;
-            const uint64_t *cgap = gapped ? c.gap.bstart : nullptr;
-            // only the buckets either key set can occupy (a rank of a multi-GPU build owns ~1/P of them: the
-            // other workgroups only wrote index entries, 0.8 ms a rank-step at P = 8); the index entries
-            // outside them are 0 below and the merged count above
-            uint64_t mlo = 0, mhi = nb;
-            if (bp && !g1 && !gapped && rm->nc) {
-                Key<L> e[4];
-                HIP_CHECK(hipMemcpyAsync(&e[0], *keys, sizeof(Key<L>), hipMemcpyDeviceToHost, c.stream));
-                HIP_CHECK(hipMemcpyAsync(&e[1], *keys + (n - 1), sizeof(Key<L>), hipMemcpyDeviceToHost, c.stream));
-                HIP_CHECK(hipMemcpyAsync(&e[2], rm->ck, sizeof(Key<L>), hipMemcpyDeviceToHost, c.stream));
-                HIP_CHECK(hipMemcpyAsync(&e[3], rm->ck + (rm->nc - 1), sizeof(Key<L>), hipMemcpyDeviceToHost, c.stream));
-                HIP_CHECK(hipStreamSynchronize(c.stream));
-                auto top = [&](const Key<L> &x) { return bits_at(shr(x, nbits - bp), 0, 32); };
-                mlo = std::min(top(e[0]), top(e[2])) << (bb - bp);
-                mhi = std::min<uint64_t>(nb, (std::max(top(e[1]), top(e[3])) + 1) << (bb - bp));
-                if (istart && mlo < mhi) {
-                    const uint64_t ilo = mlo << (rm->ib - bb), ihi = mhi << (rm->ib - bb), iend = 1ull << rm->ib;
-                    if (ilo) fill_u64_kernel<<<dim3((unsigned)std::min<uint64_t>(ceil_div(ilo, 256), 4096)), dim3(256), 0,
-                                               c.stream>>>(istart, 0, ilo, 0);
-                    if (ihi < iend)
-                        fill_u64_kernel<<<dim3((unsigned)std::min<uint64_t>(ceil_div(iend - ihi, 256), 4096)), dim3(256),
-                                          0, c.stream>>>(istart, ihi, iend, n + rm->nc);
-                    HIP_CHECK(hipGetLastError());
-                } else if (mlo >= mhi) {
-                    mlo = 0, mhi = nb;
-                }
-            }
-            bucket_pieces(mlo, mhi, [&](uint64_t g0, unsigned cnt) {
-                local_merge_kernel<L, COUNTED, CAP><<<dim3(cnt), dim3(512), 0, c.stream>>>(
-                    sa, sac, bstart, nullptr, nullptr, ck, rm->cv, cidx.start, rm->out, rm->outc, olist,
-                    &c.small->counter, bb, nbits, rm->ib, istart, cur, gbase, cgap, g0, c.merge_it);
-                HIP_CHECK(hipGetLastError());
-            });
-            uint32_t novf = 0;
-            HIP_CHECK(hipMemcpyAsync(&novf, &c.small->counter, 4, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));
-            if (novf) {  // the few big groups again with twice the LDS arrays, from the device-side list
-                const uint32_t nlist = novf;
-                HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-                bucket_pieces(0, nlist, [&](uint64_t g0, unsigned cnt) {
-                    local_merge_kernel<L, COUNTED, 2 * CAP><<<dim3(cnt), dim3(512), 0, c.stream>>>(
-                        sa, sac, bstart, nullptr, olist + g0, ck, rm->cv, cidx.start, rm->out, rm->outc, nullptr,
-                        &c.small->counter, bb, nbits, rm->ib, istart, cur, gbase, cgap, 0, c.merge_it);
-                    HIP_CHECK(hipGetLastError());
-                });
-                HIP_CHECK(hipMemcpyAsync(&novf, &c.small->counter, 4, hipMemcpyDeviceToHost, c.stream));
-                HIP_CHECK(hipStreamSynchronize(c.stream));
-            }
-            if (novf) {
-                if (c.debug) fprintf(stderr, "[mtg debug] speculative rc level: %u groups overflowed, exact level\n", novf);
-                c.radix_ms = 0, c.radix_launches = 0, c.radix_bytes = 0;
-                ++c.timings.spec_fallbacks;
-                return ~0ull;
-            }
-            rm->done = true;
-            ++c.timings.spec_levels;
-            if (fine) ++c.timings.spec_fine_levels;
-            if (gapped) c.gap.valid = false;  // merged: the canonical set is not needed compact
-            if (istart) {  // index end = the merged count (a kernel argument: no host copy to wait for)
-                const uint64_t R = n + rm->nc;
-                set_u64_kernel<<<dim3(1), dim3(1), 0, c.stream>>>(istart + (1ull << rm->ib), R);
-                HIP_CHECK(hipGetLastError());
-                note_bucket_index(c, rm->out, R, istart, nbits - rm->ib);
-            }
-            if (c.debug)
-                fprintf(stderr, "[mtg debug] speculative rc level: n=%lu capacity=%lu -> merged %lu\n", (unsigned long)n,
-                        (unsigned long)C, (unsigned long)(n + rm->nc));
-            return n;
-        }
-        // every bucket one group: [bstart[b], cur[b])
-        Key<L> *sb = inplace ? sa : (Key<L> *)c.ws.get(Workspace::SPEC_B, C * sizeof(Key<L>));
-        uint32_t *sbc = !COUNTED ? nullptr : inplace ? sac : (uint32_t *)c.ws.get(Workspace::SPEC_BC, C * 4);
-        uint32_t *ucount = (uint32_t *)c.ws.get(Workspace::MSD_UCOUNT, (nb + 1) * 4);
-        uint32_t *ovf = (uint32_t *)c.ws.get(Workspace::MSD_OVF, nb * 4);
-        HIP_CHECK(hipMemsetAsync(ovf, 0, nb * 4, c.stream));
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        const bool keycas = nbits < 64;
-        constexpr int WPE = COUNTED ? 1 : MTG_LU_WPE;  // (the uncounted table fits 8 waves per SIMD at 64 VGPRs)
-        // only the buckets the keys can occupy (blo, bhi above; a round of the batched collect fills a
-        // fraction of them); the others count 0 keys
-        HIP_CHECK(hipMemsetAsync(ucount, 0, (nb + 1) * 4, c.stream));
-        bucket_pieces(blo, bhi, [&](uint64_t g0, unsigned cnt) {
-            if (keycas && c.lu_fast)
-                local_unique_kernel<1, COUNTED, true, 512, LocalTraits<1>::SLOTS / 2, false, WPE, true, false>
-                    <<<dim3(cnt), dim3(512), 0, c.stream>>>(sa, sac, bstart, nullptr, nbits, bb, 0, sb, sbc, ucount, ovf,
-                                                            &c.small->counter, cmax, cur, g0);
-            else if (keycas)
-                local_unique_kernel<1, COUNTED, true, 512, LocalTraits<1>::SLOTS / 2, false, WPE>
-                    <<<dim3(cnt), dim3(512), 0, c.stream>>>(sa, sac, bstart, nullptr, nbits, bb, 0, sb, sbc, ucount, ovf,
-                                                            &c.small->counter, cmax, cur, g0);
-            else
-                local_unique_kernel<1, COUNTED, false, 512, LocalTraits<1>::SLOTS / 2, false, 1>
-                    <<<dim3(cnt), dim3(512), 0, c.stream>>>(sa, sac, bstart, nullptr, nbits, bb, 0, sb, sbc, ucount, ovf,
-                                                            &c.small->counter, cmax, cur, g0);
-            HIP_CHECK(hipGetLastError());
-        });
-        uint32_t novf = 0;
-        HIP_CHECK(hipMemcpyAsync(&novf, &c.small->counter, 4, hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        if (c.spec_lu_fail) novf = 1;  // MTG_SPEC_LU_FAIL=1 (tests): as if a group had overflowed
-        if (novf) {
-            if (c.debug) fprintf(stderr, "[mtg debug] speculative level: %u groups overflowed, exact level\n", novf);
-            c.radix_ms = 0, c.radix_launches = 0, c.radix_bytes = 0;
-            ++c.timings.spec_fallbacks;
-            return ~0ull;
-        }
-        uint64_t *ustart = (uint64_t *)c.ws.get(Workspace::MSD_USTART, (nb + 1) * 8);
-        {
-            uint32_t ep;
-            const uint64_t st = ceil_div(nb, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(ucount, nb, ustart, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-        }
-        if (!COUNTED && c.defer_gather_req && c.defer_gather && c.want_gidx) {
-            // the fused rc merge follows: leave the distinct keys in their buckets (Ctx::gap); the
-            // compact index of bucket g is ustart[g] (one bucket per group)
-            uint64_t *gb = (uint64_t *)c.ws.get(Workspace::GAP_BSTART, (nb + 1) * 8);
-            uint64_t *gu = (uint64_t *)c.ws.get(Workspace::GAP_USTART, (nb + 2) * 8);
-            HIP_CHECK(hipMemcpyAsync(gb, bstart, (nb + 1) * 8, hipMemcpyDeviceToDevice, c.stream));
-            HIP_CHECK(hipMemcpyAsync(gu, ustart, (nb + 1) * 8, hipMemcpyDeviceToDevice, c.stream));
-            HIP_CHECK(hipMemcpyAsync(gu + nb + 1, ustart + nb, 8, hipMemcpyDeviceToDevice, c.stream));
-            const uint64_t u = read_u64(c, (const unsigned long long *)(ustart + nb));
-            c.gap = Ctx::GappedSet{true, sb, *keys, u, nb, gb, gu};
-            consumed_gap1();
-            ++c.timings.spec_levels;
-            if (fine) ++c.timings.spec_fine_levels;
-            c.gidx = Ctx::GroupIndex{*keys, u, bb, nbits, gu};
-            if (c.debug)
-                fprintf(stderr, "[mtg debug] speculative level: n=%lu capacity=%lu (%.2fx) -> %lu distinct, left in buckets\n",
-                        (unsigned long)n, (unsigned long)C, (double)C / (double)n, (unsigned long)u);
-            return u;
-        }
-        const bool index = c.want_gidx;
-        // a collect round's share of the whole set's index (Ctx::ridx), its buckets 2^(bits - bb) a group
-        const bool rindex = !index && c.ridx.start && bb <= c.ridx.bits;
-        uint64_t *gi = index ? (uint64_t *)c.ws.get(Workspace::CANON_IDX, (nb + 2) * 8) : rindex ? c.ridx.start : nullptr;
-        const unsigned ib = rindex ? c.ridx.bits : bb;
-        if (index || rindex) HIP_CHECK(hipMemsetAsync(&c.small->gidx_bad, 0, 4, c.stream));
-        if (c.sort_out && (c.sort_out_cap == ~0ull || read_u64(c, (const unsigned long long *)(ustart + nb)) <= c.sort_out_cap)) {
-            *keys = (Key<L> *)c.sort_out;  // (the caller's destination: the input is no longer read)
-            if (COUNTED) *vals = c.sort_out_vals;
-        }
-        bucket_pieces(0, nb, [&](uint64_t g0, unsigned cnt) {
-            group_gather_kernel<L, COUNTED><<<dim3(cnt), dim3(256), 0, c.stream>>>(
-                sb, sbc, bstart, ustart, *keys, COUNTED ? *vals : nullptr, nullptr, nbits - ib, gi, &c.small->gidx_bad,
-                g0, ib - bb, rindex ? c.ridx.off : 0, rindex ? c.ridx.lo : 0, rindex ? c.ridx.hi : ~0ull);
-            HIP_CHECK(hipGetLastError());
-        });
-        uint64_t u = 0;
-        uint32_t ibad = 0;
-        HIP_CHECK(hipMemcpyAsync(&u, ustart + nb, 8, hipMemcpyDeviceToHost, c.stream));
-        if (index) {
-            HIP_CHECK(hipMemcpyAsync(gi + nb, ustart + nb, 8, hipMemcpyDeviceToDevice, c.stream));
-            HIP_CHECK(hipMemcpyAsync(gi + nb + 1, ustart + nb, 8, hipMemcpyDeviceToDevice, c.stream));
-        }
-        if (index || rindex) HIP_CHECK(hipMemcpyAsync(&ibad, &c.small->gidx_bad, 4, hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        if (index && !ibad) c.gidx = Ctx::GroupIndex{*keys, u, bb, nbits, gi};
-        if (rindex) c.ridx.written = !ibad;
-        consumed_gap1();
-        ++c.timings.spec_levels;
-        if (fine) ++c.timings.spec_fine_levels;
-        if (c.debug)
-            fprintf(stderr, "[mtg debug] speculative level: n=%lu capacity=%lu (%.2fx) -> %lu distinct\n",
-                    (unsigned long)n, (unsigned long)C, (double)C / (double)n, (unsigned long)u);
-        return u;
-    }
-}
-
-// The middle level of a 3-level sort without its exact histogram pass (a 60 GB read per configs[3]
-// round): the level-2 buckets are sized from a sample with slack and rounded up to whole tiles of the
-// level-3 tiling, the keys go from *keys into them in *alt (the caller's buffer of c.spec_mid_bytes,
-// Ctx::spec_mid_into), and the padded result is marked for level 3 as the speculative level-1 layout is
-// for level 2 (Ctx::gap1_n / gap1_tv: tile t holds keys in its first tv[t] positions), with the
-// level-2 prefix range of the keys (gap1_lo / gap1_hi) for level 3's bucket range.  False (nothing the
-// caller needs touched) when it does not fit or a bucket overflowed: the exact level then.
-template <int L, bool COUNTED>
-static bool spec_mid_level(Ctx &c, Key<L> **keys, Key<L> **alt, uint64_t n, unsigned nbits, unsigned bp, unsigned bb) {
-    if constexpr (L != 1 || COUNTED) {
-        return false;
-    } else {
-        constexpr int TILE = MsdTraits<L>::TILE;
-        constexpr uint32_t SS = 8;
-        const uint64_t tiles = ceil_div(n, TILE);
-        if (c.use_lsd || !c.spec_final || tiles < 64 * SS || bb - bp > 9 || bb > 24 || !bp) return false;
-        const uint64_t nb = 1ull << bb;
-        uint32_t *h = (uint32_t *)c.ws.get(Workspace::MSD_COUNTS, nb * 4);
-        HIP_CHECK(hipMemsetAsync(h, 0, nb * 4, c.stream));
-        // every 8th tile (level-1 buckets span hundreds of tiles here)
-        msd_hist_kernel<L><<<dim3((unsigned)ceil_div(tiles, SS)), dim3(MSD_BLOCK), 0, c.stream>>>(*keys, n, nbits, bb, bp, h,
-                                                                                                SS, 1, 1, nullptr);
-        HIP_CHECK(hipGetLastError());
-        Key<L> ends[2];
-        HIP_CHECK(hipMemcpyAsync(&ends[0], *keys, sizeof(Key<L>), hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipMemcpyAsync(&ends[1], *keys + (n - 1), sizeof(Key<L>), hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        const uint64_t lo1 = ends[0].w[0] >> (nbits - bp), hi1 = ends[1].w[0] >> (nbits - bp);
-        const uint64_t blo = lo1 << (bb - bp), bhi = std::min<uint64_t>(nb, (hi1 + 1) << (bb - bp));
-        uint32_t *cap = (uint32_t *)c.ws.get(Workspace::SPEC_CAP, nb * 4);
-        spec_caps_kernel<<<dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, c.stream>>>(h, nb, SS, cap, c.spec_tiny, blo,
-                                                                                        bhi, (uint32_t)TILE);
-        HIP_CHECK(hipGetLastError());
-        uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::MSD_BSTART, (nb + 1) * 8);
-        {
-            uint32_t ep;
-            const uint64_t st = ceil_div(nb, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(cap, nb, bstart, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-        }
-        const uint64_t C = read_u64(c, (const unsigned long long *)(bstart + nb));
-        if (C * sizeof(Key<L>) > c.spec_mid_bytes) {
-            if (c.debug) fprintf(stderr, "[mtg debug] speculative middle level: capacity %lu does not fit\n", (unsigned long)C);
-            return false;
-        }
-        auto *cur = (unsigned long long *)c.ws.get(Workspace::SPEC_CUR, nb * 8);
-        HIP_CHECK(hipMemcpyAsync(cur, bstart, nb * 8, hipMemcpyDeviceToDevice, c.stream));
-        HIP_CHECK(hipMemsetAsync(&c.small->spec_ovf, 0, 4, c.stream));
-        msd_partition_kernel<L, false><<<dim3((unsigned)xcd_grid(tiles)), dim3(MSD_BLOCK), 0, c.stream>>>(
-            *keys, *alt, nullptr, nullptr, n, nbits, bb, bp, cur, 1, (const unsigned long long *)(bstart + 1),
-            &c.small->spec_ovf, nullptr);
-        HIP_CHECK(hipGetLastError());
-        const uint64_t ntv = C / TILE;
-        uint32_t *tv = (uint32_t *)c.ws.get(Workspace::SPEC_MID_TV, std::max<uint64_t>(ntv, 1) * 4);
-        spec_tile_fill_kernel<<<dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, c.stream>>>(bstart, cur, nb, TILE, tv);
-        HIP_CHECK(hipGetLastError());
-        uint32_t povf = 0;
-        HIP_CHECK(hipMemcpyAsync(&povf, &c.small->spec_ovf, 4, hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        if (povf) {
-            if (c.debug) fprintf(stderr, "[mtg debug] speculative middle level: a bucket overflowed, exact level\n");
-            ++c.timings.spec_fallbacks;
-            return false;
-        }
-        std::swap(*keys, *alt);
-        c.gap1_n = C;
-        c.gap1_tv = tv;
-        c.gap1_lo = blo, c.gap1_hi = bhi;
-        ++c.timings.spec_levels;
-        if (c.debug)
-            fprintf(stderr, "[mtg debug] speculative middle level: n=%lu capacity=%lu (%.2fx)\n", (unsigned long)n,
-                    (unsigned long)C, (double)C / (double)n);
-        return true;
-    }
-}
-
-template <int L, bool COUNTED>
-static uint64_t msd_sort_unique(Ctx &c, Key<L> **keys, Key<L> **alt, uint32_t **vals,
-                                uint32_t **valt, uint64_t n, unsigned nbits, uint32_t cmax,
-                                double dup, const uint32_t *hist1 = nullptr, bool distinct = false,
-                                const std::vector<uint64_t> *runs = nullptr, bool level1_done = false,
-                                RcMerge<L> *rm = nullptr, const MsdPlan *force_plan = nullptr) {
-    // level1_done: the producer already scattered the keys by the plan's level-1 digit
-    // (extract_partition_kernel); hist1 holds that level's counts
-    // hist1: counts of the top plan.digit_end[1] bits of the input, when its producer made them;
-    // distinct: the input has no duplicates (the local pass skips its hash table);
-    // runs: the input is runs->size() - 1 sorted runs at these offsets (one gather replaces
-    // the partition passes)
-    const Ctx::GroupIndex saved_gidx = c.gidx;  // the canonical sort's, for the fused rc merge below
-    c.gidx = Ctx::GroupIndex{};
-    if (n == 0) return 0;
-    // *alt == nullptr (the single build after the speculative level-1 layout): the ping-pong buffer is taken
-    // only by a path that needs it -- an exact level or the group passes -- never by the speculative level
-    auto lazy_alt = [&]() {
-        if (!*alt) *alt = (Key<L> *)c.ws.get(Workspace::KB, n * sizeof(Key<L>));
-        if (COUNTED && !*valt) *valt = (uint32_t *)c.ws.get(Workspace::CB, n * 4);
-    };
-    constexpr uint32_t LIMIT = LocalTraits<L>::LIMIT;
-    constexpr int TILE = MsdTraits<L>::TILE;
-    const uint64_t tiles = ceil_div(n, TILE);
-    // force_plan: the caller fixed the digits (the routed multi-GPU collect: level 1 is the routing digit)
-    const MsdPlan plan = force_plan ? *force_plan : msd_plan<L>(c, n, nbits, dup);
-    unsigned levels = plan.levels;
-    unsigned digit_end[4] = {plan.digit_end[0], plan.digit_end[1], plan.digit_end[2], plan.digit_end[3]};
-    unsigned b = 0;
-    uint64_t *bstart = nullptr;
-    uint64_t nbuckets = 1;
-    auto run_level = [&](unsigned lev) {
-        if (digit_end[lev] == 0) digit_end[lev] = std::min(nbits, digit_end[lev - 1] + 8);
-        const unsigned bb = digit_end[lev], bp = digit_end[lev - 1];
-        nbuckets = 1ull << bb;
-        const uint32_t *cnt = hist1;
-        // level 2 after a speculative level-1 layout reads the padded array (c.gap1_n positions), and so
-        // does level 3 after a speculative middle level (spec_mid_level)
-        const bool g1 = c.gap1_n && (lev == 2 ? level1_done : lev == 3);
-        const uint64_t npos = g1 ? c.gap1_n : n, ltiles = g1 ? ceil_div(npos, TILE) : tiles;
-        const uint32_t *tv = g1 ? c.gap1_tv : nullptr;
-        if (lev != 1 || !hist1) {
-            uint32_t *h = (uint32_t *)c.ws.get(Workspace::MSD_COUNTS, nbuckets * 4);
-            HIP_CHECK(hipMemsetAsync(h, 0, nbuckets * 4, c.stream));
-            if (bp == 0 && nbuckets <= 512) {
-                const uint32_t nrows = (uint32_t)std::min<uint64_t>(tiles, 8192);
-                uint32_t *rows = (uint32_t *)c.ws.get(Workspace::HIST_ROWS, (uint64_t)nrows * nbuckets * 4);
-                msd_hist_rows_kernel<L><<<dim3(nrows), dim3(512), 0, c.stream>>>(*keys, n, nbits, bb, rows);
-                HIP_CHECK(hipGetLastError());
-                hist_rows_reduce_kernel<<<dim3(std::min<uint32_t>(nrows, 256), (unsigned)ceil_div(nbuckets, 256)),
-                                          dim3(256), 0, c.stream>>>(rows, nrows, (uint32_t)nbuckets, h);
-            } else {
-                msd_hist_kernel<L><<<dim3((unsigned)ltiles), dim3(MSD_BLOCK), 0, c.stream>>>(*keys, npos, nbits, bb, bp,
-                                                                                             h, 1, 1, 1, tv);
-            }
-            HIP_CHECK(hipGetLastError());
-            cnt = h;
-        }
-        bstart = (uint64_t *)c.ws.get(Workspace::MSD_BSTART, (nbuckets + 1) * 8);
-        uint32_t ep;
-        const uint64_t st = ceil_div(nbuckets, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(cnt, nbuckets, bstart, desc, ep,
-                                                                      &c.small->counter, &c.small->error);
-        HIP_CHECK(hipGetLastError());
-        if (lev == 1 && level1_done) {
-            b = bb;
-            return;
-        }
-        lazy_alt();  // (a partition level writes *alt)
-        auto *cur = (unsigned long long *)c.ws.get(Workspace::MSD_CURSOR, nbuckets * 8);
-        HIP_CHECK(hipMemcpyAsync(cur, bstart, nbuckets * 8, hipMemcpyDeviceToDevice, c.stream));
-        EventTimer tm(c.stream);
-        tm.mark();
-        // 512-thread tiles (8 K keys, two workgroups per CU) on XCD-contiguous tiles: 3.77 ms for the
-        // cfg2 level-2 pass vs 4.09 with 1024-thread tiles (16 K keys, one per CU) -- before the XCD
-        // mapping the longer runs of the big tiles won (4.65 vs 5.3 ms); nontemporal access measured
-        // the same (tools/part_bench.hip)
-        msd_partition_kernel<L, COUNTED><<<dim3((unsigned)xcd_grid(ltiles)), dim3(MSD_BLOCK), 0, c.stream>>>(
-            *keys, *alt, COUNTED ? *vals : nullptr, COUNTED ? *valt : nullptr, npos, nbits, bb, bp, cur, 1, nullptr,
-            nullptr, tv);
-        HIP_CHECK(hipGetLastError());
-        if (g1) c.gap1_n = 0, c.gap1_tv = nullptr, c.gap1_lo = c.gap1_hi = 0;  // compact from here on
-        tm.mark();
-        if (c.track_partition && c.radix_launches == 0) {  // first partition launch of the sort
-            HIP_CHECK(hipStreamSynchronize(c.stream));
-            c.radix_ms += tm.ms(0, 1);
-            c.radix_launches += 1;
-            c.radix_bytes += 2.0 * n * (sizeof(Key<L>) + (COUNTED ? 4 : 0));
-        }
-        std::swap(*keys, *alt);
-        if (COUNTED) std::swap(*vals, *valt);
-        b = bb;
-    };
-    if (runs && runs->size() >= 2 && runs->size() <= 129 && levels) {
-        lazy_alt();
-        // bucket layout of the top T bits straight from the runs' own order
-        const unsigned T = digit_end[levels];
-        const uint32_t P = (uint32_t)runs->size() - 1;
-        nbuckets = 1ull << T;
-        uint64_t *idx = (uint64_t *)c.ws.get(Workspace::RUN_IDX, (uint64_t)P * (nbuckets + 1) * 8);
-        int64_t *delta = (int64_t *)c.ws.get(Workspace::RUN_DELTA, (uint64_t)P * nbuckets * 8);
-        for (uint32_t j = 0; j < P; ++j) {
-            const uint64_t r0 = (*runs)[j], rn = (*runs)[j + 1] - r0;
-            bucket_index<L>(c, *keys + r0, rn, nbits - T, nbuckets, idx + (uint64_t)j * (nbuckets + 1));
-        }
-        bstart = (uint64_t *)c.ws.get(Workspace::MSD_BSTART, (nbuckets + 1) * 8);
-        runs_delta_kernel<<<dim3((unsigned)std::min<uint64_t>(ceil_div(nbuckets + 1, 256), 16384)), dim3(256), 0,
-                            c.stream>>>(idx, P, nbuckets, bstart, delta);
-        HIP_CHECK(hipGetLastError());
-        uint64_t *droff = (uint64_t *)c.ws.get(Workspace::RUN_OFF, (P + 1) * 8);
-        HIP_CHECK(hipMemcpyAsync(droff, runs->data(), (P + 1) * 8, hipMemcpyHostToDevice, c.stream));
-        runs_gather_kernel<L, COUNTED><<<dim3((unsigned)std::min<uint64_t>(ceil_div(n, 256), 65536)), dim3(256), 0,
-                                         c.stream>>>(*keys, COUNTED ? *vals : nullptr, n, droff, P, delta,
-                                                     nbuckets, nbits, T, *alt, COUNTED ? *valt : nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(c.stream));  // `runs` is the caller's host vector
-        std::swap(*keys, *alt);
-        if (COUNTED) std::swap(*vals, *valt);
-        b = T;
-    } else {
-        for (unsigned lev = 1; lev <= levels; ++lev) {
-            // the last of 2 or 3 levels, the ones before it in place (3 levels: inputs over ~1.6e9 keys)
-            // (any plain sort + unique too: configs[4]'s KMC records have no fused level 1)
-            if (lev == levels && lev >= 2 && (lev == 2 || c.spec3) && (level1_done || (rm && distinct) || (!rm && !distinct))) {
-                // the per-tile (fine) sample when the previous level's buckets span few tiles: 3 levels, or
-                // a 10-bit level 1 on a small input (a tile-granular sample of ~30 tiles a bucket missed
-                // by up to ~25 %)
-                const bool fine = lev >= 3 || (n >> digit_end[lev - 1]) < 64ull * MsdTraits<L>::TILE;
-                // the caller's spare buffer (c.spec_into) once level 2 has moved the keys out of it
-                Key<L> *spare = lev >= 3 && c.spec_into && c.spec_into != (void *)*keys ? (Key<L> *)c.spec_into : nullptr;
-                const uint64_t u = spec_final_level<L, COUNTED>(c, keys, vals, n, nbits, digit_end[lev - 1],
-                                                                digit_end[lev], cmax, distinct, rm, saved_gidx, fine,
-                                                                spare);
-                if (u != ~0ull) return u;
-            }
-            // a 3-level sort's middle level without its histogram pass, into the caller's buffer
-            if (lev == 2 && levels == 3 && level1_done && !c.gap1_n && c.spec_mid && c.spec3 && *alt &&
-                c.spec_mid_into == (void *)*alt &&
-                spec_mid_level<L, COUNTED>(c, keys, alt, n, nbits, digit_end[1], digit_end[2])) {
-                b = digit_end[2];
-                continue;
-            }
-            run_level(lev);
-        }
-    }
-
-    lazy_alt();
-    while (true) {
-        // groups of consecutive buckets holding <= G keys; bigger buckets stand alone
-        const uint64_t G = LIMIT / 4;
-        uint64_t ngroups = 1;
-        uint64_t *gstart;
-        const uint64_t *gbucket_out = nullptr;
-        if (b == 0) {
-            gstart = (uint64_t *)c.ws.get(Workspace::MSD_GSTART, 16);
-            set_pair_kernel<<<1, 1, 0, c.stream>>>(gstart, 0, n);
-            HIP_CHECK(hipGetLastError());
-        } else {
-            uint32_t *gf = (uint32_t *)c.ws.get(Workspace::MSD_UCOUNT, (nbuckets + 1) * 4);
-            const bool fuse = rm && distinct && b <= 32;
-            uint64_t *cstart = nullptr;
-            const uint64_t *gsize = bstart;
-            if (fuse) {
-                ensure_compact(c);  // this path reads the canonical keys compact
-                // fused rc merge: the canonical keys of every bucket (bucket index of the sorted
-                // set), and groups sized by rc + canonical keys together
-                if (saved_gidx.keys == (const void *)rm->ck && saved_gidx.n == rm->nc && saved_gidx.bits == b &&
-                    saved_gidx.nbits == nbits) {
-                    cstart = const_cast<uint64_t *>(saved_gidx.start);  // the canonical sort's group starts
-                } else {
-                    cstart = (uint64_t *)c.ws.get(Workspace::RC_CSTART, (nbuckets + 2) * 8);
-                    bucket_index<L>(c, rm->ck, rm->nc, nbits - b, nbuckets, cstart);
-                }
-                uint64_t *comb = (uint64_t *)c.ws.get(Workspace::RC_COMB, (nbuckets + 1) * 8);
-                add_starts_kernel<<<dim3((unsigned)ceil_div(nbuckets + 1, 256)), dim3(256), 0, c.stream>>>(
-                    bstart, cstart, nbuckets + 1, comb);
-                HIP_CHECK(hipGetLastError());
-                gsize = comb;
-            }
-            group_flags_kernel<<<dim3((unsigned)ceil_div(nbuckets, 256)), dim3(256), 0, c.stream>>>(
-                gsize, nbuckets, G, gf);
-            HIP_CHECK(hipGetLastError());
-            uint64_t *gpos = (uint64_t *)c.ws.get(Workspace::MSD_USTART, (nbuckets + 1) * 8);
-            uint32_t ep;
-            const uint64_t st = ceil_div(nbuckets, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(gf, nbuckets, gpos, desc, ep,
-                                                                          &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(&ngroups, gpos + nbuckets, 8, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));
-            gstart = (uint64_t *)c.ws.get(Workspace::MSD_GSTART, (ngroups + 1) * 8);
-            // each group's bucket range: the fused rc merge's canonical ranges, or the output's bucket index
-            uint64_t *gbucket = b <= 32 ? (uint64_t *)c.ws.get(Workspace::MSD_GBUCKET, (ngroups + 1) * 8) : nullptr;
-            gbucket_out = gbucket;
-            group_scatter_kernel<<<dim3((unsigned)ceil_div(nbuckets + 1, 256)), dim3(256), 0, c.stream>>>(
-                bstart, gf, gpos, nbuckets, n, gstart, gbucket);
-            HIP_CHECK(hipGetLastError());
-            if (fuse && ngroups) {
-                // sort the rc groups and merge them with the canonical keys in one pass
-                constexpr int CAP = MergeLocalTraits<L>::CAP;
-                uint32_t *olist = (uint32_t *)c.ws.get(Workspace::MSD_OVF, ngroups * 4);  // overflowing groups
-                HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-                uint64_t *istart = rm->istart && rm->ib >= b ? rm->istart : nullptr;
-                bucket_pieces(0, ngroups, [&](uint64_t g0, unsigned cnt) {
-                    local_merge_kernel<L, COUNTED, CAP><<<dim3(cnt), dim3(512), 0, c.stream>>>(
-                        *keys, COUNTED ? *vals : nullptr, gstart, gbucket, nullptr, rm->ck, rm->cv, cstart, rm->out,
-                        rm->outc, olist, &c.small->counter, b, nbits, rm->ib, istart, nullptr, nullptr, nullptr, g0,
-                        c.merge_it);
-                    HIP_CHECK(hipGetLastError());
-                });
-                uint32_t novf = 0;
-                HIP_CHECK(hipMemcpyAsync(&novf, &c.small->counter, 4, hipMemcpyDeviceToHost, c.stream));
-                HIP_CHECK(hipStreamSynchronize(c.stream));
-                if (novf) {  // the few big groups again with twice the LDS arrays, from the device-side list
-                    const uint32_t nlist = novf;
-                    HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-                    bucket_pieces(0, nlist, [&](uint64_t g0, unsigned cnt) {
-                        local_merge_kernel<L, COUNTED, 2 * CAP><<<dim3(cnt), dim3(512), 0, c.stream>>>(
-                            *keys, COUNTED ? *vals : nullptr, gstart, gbucket, olist + g0, rm->ck, rm->cv, cstart,
-                            rm->out, rm->outc, nullptr, &c.small->counter, b, nbits, rm->ib, istart, nullptr, nullptr,
-                            nullptr, 0, c.merge_it);
-                        HIP_CHECK(hipGetLastError());
-                    });
-                    HIP_CHECK(hipMemcpyAsync(&novf, &c.small->counter, 4, hipMemcpyDeviceToHost, c.stream));
-                    HIP_CHECK(hipStreamSynchronize(c.stream));
-                    if (c.debug) fprintf(stderr, "[mtg debug] rc merge: %u big groups -> %u left\n", nlist, novf);
-                }
-                if (!novf) {
-                    rm->done = true;
-                    if (istart) {  // index end = the merged count (a kernel argument: no host copy to wait for)
-                        const uint64_t R = n + rm->nc;
-                        set_u64_kernel<<<dim3(1), dim3(1), 0, c.stream>>>(istart + (1ull << rm->ib), R);
-                        HIP_CHECK(hipGetLastError());
-                        note_bucket_index(c, rm->out, R, istart, nbits - rm->ib);
-                    }
-                    return n;  // the rc keys (distinct); rm->out holds U + n
-                }
-            }
-        }
-        uint32_t *ucount = (uint32_t *)c.ws.get(Workspace::MSD_UCOUNT, (ngroups + 1) * 4);
-        uint32_t *ovf = (uint32_t *)c.ws.get(Workspace::MSD_OVF, ngroups * 4);
-        HIP_CHECK(hipMemsetAsync(ovf, 0, ngroups * 4, c.stream));
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        auto launch_local = [&](const uint32_t *glist, uint64_t count, unsigned sbits) {
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            auto go = [&](auto keycas, auto sl, auto nodup) {
-                constexpr bool KC = decltype(keycas)::value;
-                constexpr int SL = decltype(sl)::value;
-                constexpr bool ND = decltype(nodup)::value;
-                constexpr int WPE = (L == 1 && KC && !ND && !COUNTED) ? MTG_LU_WPE : 1;
-                bucket_pieces(0, count, [&](uint64_t g0, unsigned cnt) {
-                    if constexpr (KC && !ND) {
-                        if (c.lu_fast && sbits == 0) {  // the first launch: no key-range slices
-                            local_unique_kernel<L, COUNTED, KC, 512, SL, ND, WPE, true, false><<<dim3(cnt), dim3(512), 0, c.stream>>>(
-                                *keys, COUNTED ? *vals : nullptr, gstart, glist ? glist + g0 : nullptr, nbits, b, sbits,
-                                *alt, COUNTED ? *valt : nullptr, ucount, ovf, &c.small->counter, cmax, nullptr,
-                                glist ? 0 : g0);
-                            return;
-                        }
-                        if (c.lu_fast) {
-                            local_unique_kernel<L, COUNTED, KC, 512, SL, ND, WPE, true><<<dim3(cnt), dim3(512), 0, c.stream>>>(
-                                *keys, COUNTED ? *vals : nullptr, gstart, glist ? glist + g0 : nullptr, nbits, b, sbits,
-                                *alt, COUNTED ? *valt : nullptr, ucount, ovf, &c.small->counter, cmax, nullptr,
-                                glist ? 0 : g0);
-                            return;
-                        }
-                    }
-                    // u128 keys (configs[2]): the state-word table at <= 80 VGPRs, so three workgroups fit a CU
-                    // (the LDS allows three; 93 VGPRs allowed two)
-                    if constexpr (L == 2 && !KC && !ND && !COUNTED) {
-                        if (c.lu_wpe2) {
-                            local_unique_kernel<L, COUNTED, KC, 512, SL, ND, 6><<<dim3(cnt), dim3(512), 0, c.stream>>>(
-                                *keys, COUNTED ? *vals : nullptr, gstart, glist ? glist + g0 : nullptr, nbits, b, sbits,
-                                *alt, COUNTED ? *valt : nullptr, ucount, ovf, &c.small->counter, cmax, nullptr,
-                                glist ? 0 : g0);
-                            return;
-                        }
-                    }
-                    local_unique_kernel<L, COUNTED, KC, 512, SL, ND, WPE><<<dim3(cnt), dim3(512), 0, c.stream>>>(
-                        *keys, COUNTED ? *vals : nullptr, gstart, glist ? glist + g0 : nullptr, nbits, b, sbits, *alt,
-                        COUNTED ? *valt : nullptr, ucount, ovf, &c.small->counter, cmax, nullptr, glist ? 0 : g0);
-                });
-            };
-            using T_ = std::true_type;
-            using F_ = std::false_type;
-            using SHalf = std::integral_constant<int, LocalTraits<L>::SLOTS / 2>;
-            const bool keycas = L == 1 && nbits < 64;
-            if (distinct) go(F_{}, SHalf{}, T_{});
-            else if (keycas) go(T_{}, SHalf{}, F_{});
-            else go(F_{}, SHalf{}, F_{});
-            HIP_CHECK(hipGetLastError());
-            uint32_t nov = 0;
-            HIP_CHECK(hipMemcpyAsync(&nov, &c.small->counter, 4, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));
-            return nov;
-        };
-        uint32_t novf = launch_local(nullptr, ngroups, 0);
-        if (c.trace)
-            fprintf(stderr, "[mtg trace] msd n=%lu levels=%u b=%u groups=%lu overflow=%u\n", (unsigned long)n, levels, b,
-                    (unsigned long)ngroups, novf);
-        if (c.debug)
-            fprintf(stderr, "[mtg debug] msd n=%lu nbits=%u levels=%u b=%u buckets=%lu groups=%lu overflow=%u\n",
-                    (unsigned long)n, nbits, levels, b, (unsigned long)nbuckets, (unsigned long)ngroups, novf);
-        // overflowing one-bucket groups: rerun them alone in 2, 4, 8, 16 key-range slices
-        std::vector<uint32_t> flags;
-        std::vector<uint64_t> gs;
-        for (unsigned sbits = 1; novf && b && sbits <= 4 && b + sbits <= nbits; ++sbits) {
-            flags.resize(ngroups);
-            HIP_CHECK(hipMemcpyAsync(flags.data(), ovf, ngroups * 4, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));
-            std::vector<uint32_t> list;
-            for (uint64_t g = 0; g < ngroups; ++g)
-                if (flags[g]) list.push_back((uint32_t)g);
-            uint32_t *dlist = (uint32_t *)c.ws.get(Workspace::MSD_GLIST, list.size() * 4);
-            HIP_CHECK(hipMemcpyAsync(dlist, list.data(), list.size() * 4, hipMemcpyHostToDevice, c.stream));
-            novf = launch_local(dlist, list.size(), sbits);  // syncs: `list` outlives the copy
-            if (c.debug) fprintf(stderr, "[mtg debug]   sliced rerun sbits=%u groups=%zu -> overflow=%u\n", sbits, list.size(), novf);
-        }
-        if (novf) {
-            flags.resize(ngroups);
-            gs.resize(ngroups + 1);
-            HIP_CHECK(hipMemcpyAsync(flags.data(), ovf, ngroups * 4, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipMemcpyAsync(gs.data(), gstart, (ngroups + 1) * 8, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));
-            uint64_t ovf_keys = 0;
-            for (uint64_t g = 0; g < ngroups; ++g)
-                if (flags[g]) ovf_keys += gs[g + 1] - gs[g];
-            if (c.debug) {
-                fprintf(stderr, "[mtg debug]   fallback: %u groups, %lu keys\n", novf, (unsigned long)ovf_keys);
-                int shown = 0;
-                for (uint64_t g = 0; g < ngroups && shown < 5; ++g)
-                    if (flags[g]) {
-                        fprintf(stderr, "[mtg debug]     group %lu [%lu, %lu)\n", (unsigned long)g,
-                                (unsigned long)gs[g], (unsigned long)gs[g + 1]);
-                        ++shown;
-                    }
-            }
-            if (ovf_keys * 20 > n && levels < 3 && digit_end[levels] < nbits) {
-                run_level(++levels);  // many overflows: one more level for everything
-                continue;
-            }
-            // the rest: LSD radix sort + unique of each group in place
-            for (uint64_t g = 0; g < ngroups; ++g) {
-                if (!flags[g]) continue;
-                const uint64_t g0 = gs[g], m = gs[g + 1] - gs[g];
-                Key<L> *fk = (Key<L> *)c.ws.get(Workspace::FB_K, m * sizeof(Key<L>));
-                uint32_t *fv = COUNTED ? (uint32_t *)c.ws.get(Workspace::FB_V, m * 4) : nullptr;
-                Key<L> *ka = *keys + g0, *kb = fk;
-                uint32_t *va = COUNTED ? *vals + g0 : nullptr, *vb = fv;
-                radix_sort<L, COUNTED>(c, &ka, &kb, &va, &vb, m, nbits, false);
-                reset_small(c);
-                const uint64_t ut = ceil_div(m, 2048);
-                uint32_t ep;
-                uint64_t *desc = acquire_desc(c, ut, &ep);
-                unsigned long long *sums = nullptr;
-                if (COUNTED) {
-                    sums = (unsigned long long *)c.ws.get(Workspace::SUMS, m * 8);
-                    HIP_CHECK(hipMemsetAsync(sums, 0, m * 8, c.stream));
-                }
-                unique_kernel<L, COUNTED><<<dim3((unsigned)ut), dim3(256), 0, c.stream>>>(
-                    ka, va, m, *alt + g0, sums, desc, ep, &c.small->counter, &c.small->total, &c.small->error);
-                HIP_CHECK(hipGetLastError());
-                const uint64_t u = read_u64(c, &c.small->total);
-                if (COUNTED)
-                    count_clamp_kernel<<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(u, 256), 4096))),
-                                         dim3(256), 0, c.stream>>>(sums, u, cmax, *valt + g0);
-                const uint32_t u32 = (uint32_t)u;
-                HIP_CHECK(hipMemcpyAsync(ucount + g, &u32, 4, hipMemcpyHostToDevice, c.stream));
-                HIP_CHECK(hipStreamSynchronize(c.stream));
-            }
-        }
-        // pack: ustart = exclusive scan of ucount, gather tmp (= *alt) -> *keys
-        uint64_t *ustart = (uint64_t *)c.ws.get(Workspace::MSD_USTART, (ngroups + 1) * 8);
-        uint32_t ep;
-        const uint64_t st = ceil_div(ngroups, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(ucount, ngroups, ustart, desc, ep,
-                                                                      &c.small->counter, &c.small->error);
-        HIP_CHECK(hipGetLastError());
-        // the output's bucket index over the top b bits comes out of the gather (the fused rc merge
-        // of the canonical keys reuses it instead of a bucket_index pass: 0.44 ms at configs[1])
-        // (only for the sorts the fused rc merge follows: c.want_gidx)
-        const bool index = c.want_gidx && gbucket_out && b > 0;
-        uint64_t *gi = index ? (uint64_t *)c.ws.get(Workspace::CANON_IDX, (nbuckets + 2) * 8) : nullptr;
-        if (index) HIP_CHECK(hipMemsetAsync(&c.small->gidx_bad, 0, 4, c.stream));
-        if (c.sort_out &&
-            (c.sort_out_cap == ~0ull || read_u64(c, (const unsigned long long *)(ustart + ngroups)) <= c.sort_out_cap)) {
-            *keys = (Key<L> *)c.sort_out;  // (the caller's destination: the gather reads *alt only)
-            if (COUNTED) *vals = c.sort_out_vals;
-        }
-        bucket_pieces(0, ngroups, [&](uint64_t g0, unsigned cnt) {
-            group_gather_kernel<L, COUNTED><<<dim3(cnt), dim3(256), 0, c.stream>>>(
-                *alt, COUNTED ? *valt : nullptr, gstart, ustart, *keys, COUNTED ? *vals : nullptr, gbucket_out,
-                nbits - b, gi, &c.small->gidx_bad, g0);
-            HIP_CHECK(hipGetLastError());
-        });
-        uint64_t u = 0;
-        uint32_t ibad = 0;
-        HIP_CHECK(hipMemcpyAsync(&u, ustart + ngroups, 8, hipMemcpyDeviceToHost, c.stream));
-        if (index) {  // entries nbuckets, nbuckets + 1 = the key count
-            HIP_CHECK(hipMemcpyAsync(gi + nbuckets, ustart + ngroups, 8, hipMemcpyDeviceToDevice, c.stream));
-            HIP_CHECK(hipMemcpyAsync(gi + nbuckets + 1, ustart + ngroups, 8, hipMemcpyDeviceToDevice, c.stream));
-            HIP_CHECK(hipMemcpyAsync(&ibad, &c.small->gidx_bad, 4, hipMemcpyDeviceToHost, c.stream));
-        }
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        if (index && !ibad) c.gidx = Ctx::GroupIndex{*keys, u, b, nbits, gi};
-        return u;
-    }
-}
-
-template <int L>
-static unsigned bucket_bits(uint64_t n, unsigned keybits) {
-    // ~4 keys a bucket; at most 2^26 buckets up to 2^30 keys (configs[1]: 5.5 a bucket), 2^29 above: at
-    // configs[3]'s share (4.7e9 real edges) 2^26 buckets held 69 edges each, and the dummy sink join's
-    // staged class ranges (whole buckets at both ends) outgrew its LDS and fell back to global searches
-    const unsigned cap = n > (1ull << 30) ? 29 : 26;
-    unsigned b = 1;
-    while (b < cap && (1ull << (b + 2)) < n) ++b;
-    return std::min(b, keybits);
-}
 
 struct BuildInput {
     const uint8_t *seq;
@@ -1757,37 +67,6 @@ struct BuildOutput {
     uint64_t n_dummy;
     bool host = false;  // the spilled build (run_pipeline_spill): W / last / weights are host arrays
 };
-
-// MTG_DEBUG=1: host-side check that a device key array is strictly increasing
-template <int L>
-static void debug_check_sorted(Ctx &c, const char *what, const Key<L> *d, uint64_t n) {
-    if (!c.debug || n == 0) return;
-    std::vector<Key<L>> h(n);
-    HIP_CHECK(hipMemcpyAsync(h.data(), d, n * sizeof(Key<L>), hipMemcpyDeviceToHost, c.stream));
-    HIP_CHECK(hipStreamSynchronize(c.stream));
-    uint64_t bad = 0;
-    for (uint64_t i = 1; i < n; ++i) bad += !(h[i - 1] < h[i]);
-    fprintf(stderr, "[mtg debug] %s: n=%lu, %lu order violations; first keys:", what,
-            (unsigned long)n, (unsigned long)bad);
-    for (uint64_t i = 0; i < std::min<uint64_t>(n, 8); ++i) fprintf(stderr, " %lx", (unsigned long)h[i].w[0]);
-    fprintf(stderr, "\n");
-}
-
-// merge of two sorted arrays through the tiled merge-path kernels (boss_kernels.hpp)
-template <int LO, int LA, bool LIFT, bool COUNTED, bool BCOUNTS>
-static void merge_sorted(Ctx &c, const Key<LA> *a, const uint32_t *ac, uint64_t na,
-                         const Key<LO> *b, const uint32_t *bc, uint64_t nb, unsigned K,
-                         Key<LO> *out, uint32_t *oc, uint64_t off) {
-    const uint64_t ntiles = ceil_div(na + nb, MergeTraits<LO>::TILE);
-    if (!ntiles) return;
-    uint64_t *splits = (uint64_t *)c.ws.get(Workspace::SPLITS, (ntiles + 1) * 8);
-    merge_partition_kernel<LO, LA, LIFT><<<dim3((unsigned)ceil_div(ntiles + 1, 256)), dim3(256), 0, c.stream>>>(
-        a, na, b, nb, K, ntiles, splits);
-    HIP_CHECK(hipGetLastError());
-    merge_kernel<LO, LA, LIFT, COUNTED, BCOUNTS><<<dim3((unsigned)ntiles), dim3(256), 0, c.stream>>>(
-        a, ac, na, b, bc, nb, K, splits, out, oc, off);
-    HIP_CHECK(hipGetLastError());
-}
 
 // ---------------------------------------------------------------------------- pipeline stages
 
@@ -1833,7 +112,7 @@ static uint64_t stage_extract(Ctx &c, unsigned K, bool canonical, uint32_t cmax,
 // Whether the reads may be one window each (K chars + a separator, read r at r * (K + 1): a KMC
 // database decoded into reads); window_reads_kernel checks every read and says if not.
 static bool window_layout(Ctx &c, unsigned K, const BuildInput &in) {
-    if (!in.read_starts || in.n_reads == 0 || c.use_lsd) return false;
+    if (!in.read_starts || in.n_reads == 0 || c.knobs.use_lsd) return false;
     const uint64_t n = in.n_reads, st = K + 1;
     if (in.seq_len < (n - 1) * st + K || in.seq_len > n * st) return false;
     uint64_t s[2] = {0, st};
@@ -1866,7 +145,7 @@ static bool stage_extract_windows(Ctx &c, unsigned K, bool canonical, uint32_t c
     HIP_CHECK(hipMemcpyAsync(&N, &c.small->wcursor, 8, hipMemcpyDeviceToHost, c.stream));
     HIP_CHECK(hipStreamSynchronize(c.stream));
     if (bad) return false;
-    if (c.debug) fprintf(stderr, "[mtg debug] one-window reads: %lu reads -> %llu k-mers\n", (unsigned long)n, N);
+    if (c.knobs.debug) fprintf(stderr, "[mtg debug] one-window reads: %lu reads -> %llu k-mers\n", (unsigned long)n, N);
     c.timings.n_positions = in.seq_len >= K ? in.seq_len - K + 1 : 0;
     c.timings.n_extracted = N;
     *N_out = N;
@@ -1883,8 +162,8 @@ static MsdPlan fused_plan(const Ctx &c, uint64_t N, unsigned nbits, double dup, 
     if (!p.levels || !fast) return p;
     const unsigned T = p.digit_end[p.levels];
     unsigned b1 = 0;
-    if (c.fused_b1) b1 = std::min(c.fused_b1, T);
-    else if (c.wide_b1 && p.levels == 3 && !c.min_levels && T <= 10 + MSD_DBITS) b1 = 10;
+    if (c.knobs.fused_b1) b1 = std::min(c.knobs.fused_b1, T);
+    else if (c.knobs.wide_b1 && p.levels == 3 && !c.knobs.min_levels && T <= 10 + MSD_DBITS) b1 = 10;
     if (!b1) return p;
     MsdPlan q{};
     q.levels = 1 + (T - b1 + MSD_DBITS - 1) / MSD_DBITS;
@@ -1907,7 +186,7 @@ struct FusedA {
 };
 
 static bool fused_applies(const Ctx &c, unsigned K, uint64_t npos, unsigned kmax = 32) {
-    return c.fused && !c.use_lsd && npos >= c.fused_min && npos >= 4096 && K - 1 >= FUSED_HB / 2 && K <= kmax;
+    return c.knobs.fused && !c.knobs.use_lsd && npos >= c.knobs.fused_min && npos >= 4096 && K - 1 >= FUSED_HB / 2 && K <= kmax;
 }
 
 // pass A over every window, and the duplication estimate from a sample of windows (on a side stream
@@ -1917,26 +196,26 @@ static bool fused_applies(const Ctx &c, unsigned K, uint64_t npos, unsigned kmax
 template <bool OTHER, typename... A>
 static void launch_hist_fast(const Ctx &c, unsigned K, dim3 g, dim3 b, const uint8_t *seq, uint64_t seq_len,
                              unsigned K_, int cm, A... a) {
-    if (K == 31 && c.kspec && cm == 0) extract_hist_fast_kernel<OTHER, 31, 0><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
-    else if (K == 31 && c.kspec && cm == 1) extract_hist_fast_kernel<OTHER, 31, 1><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
-    else if (K == 31 && c.kspec && cm == 2) extract_hist_fast_kernel<OTHER, 31, 2><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
+    if (K == 31 && c.knobs.kspec && cm == 0) extract_hist_fast_kernel<OTHER, 31, 0><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
+    else if (K == 31 && c.knobs.kspec && cm == 1) extract_hist_fast_kernel<OTHER, 31, 1><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
+    else if (K == 31 && c.knobs.kspec && cm == 2) extract_hist_fast_kernel<OTHER, 31, 2><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
     else extract_hist_fast_kernel<OTHER, 0><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
 }
 template <int BLOCK, int NB, typename... A>
 static void launch_part_fast(const Ctx &c, unsigned K, dim3 g, dim3 b, const uint8_t *seq, uint64_t seq_len,
                              unsigned K_, int cm, A... a) {
-    if (K == 31 && c.kspec && cm == 0)
+    if (K == 31 && c.knobs.kspec && cm == 0)
         extract_partition_fast_kernel<BLOCK, NB, 31, 0><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
-    else if (K == 31 && c.kspec && cm == 1)
+    else if (K == 31 && c.knobs.kspec && cm == 1)
         extract_partition_fast_kernel<BLOCK, NB, 31, 1><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
-    else if (K == 31 && c.kspec && cm == 2)
+    else if (K == 31 && c.knobs.kspec && cm == 2)
         extract_partition_fast_kernel<BLOCK, NB, 31, 2><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
     else
         extract_partition_fast_kernel<BLOCK, NB, 0><<<g, b, 0, c.stream>>>(seq, seq_len, K_, cm, a...);
 }
 
 // sample > 1 (fused_pass_b_spec): every row counts every sample-th of its tiles, and the 2048 rows form
-// c.spec_l1_stripes stripes (A->h, A->N are then estimates)
+// c.knobs.spec_l1_stripes stripes (A->h, A->N are then estimates)
 constexpr uint32_t kSpecRows = 2048;
 static void fused_pass_a(Ctx &c, unsigned K, bool canonical, const BuildInput &in, FusedA *A, uint32_t sample = 1,
                          int fbk = 512) {
@@ -1964,7 +243,7 @@ static void fused_pass_a(Ctx &c, unsigned K, bool canonical, const BuildInput &i
     // before the XCD mapping (their longer runs: PMC writes 1.16 vs 1.30 x N w)
     const uint32_t rps = (uint32_t)(16 * fbk / TILE);
     // (stripe_cursor_kernel takes at most 1024 stripes: 2048 rows at rps = 2, 1024 at rps = 1)
-    uint32_t nrows = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(tiles, c.hist_rows), 1024ull * rps);
+    uint32_t nrows = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(tiles, c.knobs.hist_rows), 1024ull * rps);
     if (nrows >= rps) nrows -= nrows % rps;
     const unsigned hb = FUSED_HB;
     const uint32_t nbh = 1u << hb;
@@ -1984,7 +263,7 @@ static void fused_pass_a(Ctx &c, unsigned K, bool canonical, const BuildInput &i
         // S stripes of kSpecRows / S rows: row r counts the pass-A tiles [r per_row, (r + 1) per_row),
         // so stripe s (pass-B tiles [s per_stripe, (s + 1) per_stripe), 2 pass-A tiles each) is rows
         // s rps .. + rps - 1
-        const uint32_t S = c.spec_l1_stripes, srps = kSpecRows / S;
+        const uint32_t S = c.knobs.spec_l1_stripes, srps = kSpecRows / S;
         nrows = kSpecRows;
         rows = (uint32_t *)c.ws.get(Workspace::HIST_ROWS, (uint64_t)nrows * nbh * 4);
         per_row = ceil_div(tiles, nrows);
@@ -1993,7 +272,7 @@ static void fused_pass_a(Ctx &c, unsigned K, bool canonical, const BuildInput &i
         rps_out = srps;
     }
     if (K > 32) {
-        if (K == 63 && c.kspec)
+        if (K == 63 && c.knobs.kspec)
             extract_hist_wide_kernel<63><<<dim3(nrows), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, cmode(c, canonical),
                                                                               tiles, per_row, rows, sample);
         else
@@ -2041,7 +320,7 @@ struct BucketSel {
 // the u128 pass B as the packed-word kernel (extract_partition_fast2_kernel): uncounted basic / canonical
 template <int L, bool COUNTED>
 static inline bool fast2_applies(const Ctx &c, unsigned K, bool canonical) {
-    return L == 2 && !COUNTED && c.fast2 && K > 32 && K <= 64 && cmode(c, canonical) <= 1;
+    return L == 2 && !COUNTED && c.knobs.fast2 && K > 32 && K <= 64 && cmode(c, canonical) <= 1;
 }
 
 // pass B: the k-mers whose level-1 bucket (top b1 bits) is in `sel` (nullptr: every bucket)
@@ -2102,15 +381,15 @@ static uint64_t fused_pass_b(Ctx &c, unsigned K, bool canonical, uint32_t cmax, 
         if (fast2_applies<L, COUNTED>(c, K, canonical)) {
             // the same 4096-window tiles as 512 threads of 8 windows (twice the waves a CU at the same LDS)
             static_assert(FusedTraits<COUNTED, B>::TILE == 512 * 8, "a pass-B tile = 512 threads x 8 windows");
-            if (c.fast2_ppt8 && K == 63 && c.kspec)
+            if (c.knobs.fast2_ppt8 && K == 63 && c.knobs.kspec)
                 extract_partition_fast2_kernel<512, 63, 8><<<dim3((unsigned)xcd_grid(ftiles)), dim3(512), 0, c.stream>>>(
                     in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
                     (const uint32_t *)dsel, bdelta);
-            else if (c.fast2_ppt8)
+            else if (c.knobs.fast2_ppt8)
                 extract_partition_fast2_kernel<512, 0, 8><<<dim3((unsigned)xcd_grid(ftiles)), dim3(512), 0, c.stream>>>(
                     in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
                     (const uint32_t *)dsel, bdelta);
-            else if (K == 63 && c.kspec)
+            else if (K == 63 && c.knobs.kspec)
                 extract_partition_fast2_kernel<B, 63><<<dim3((unsigned)xcd_grid(ftiles)), dim3(B), 0, c.stream>>>(
                     in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
                     (const uint32_t *)dsel, bdelta);
@@ -2118,7 +397,7 @@ static uint64_t fused_pass_b(Ctx &c, unsigned K, bool canonical, uint32_t cmax, 
                 extract_partition_fast2_kernel<B><<<dim3((unsigned)xcd_grid(ftiles)), dim3(B), 0, c.stream>>>(
                     in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
                     (const uint32_t *)dsel, bdelta);
-        } else if (K == 63 && c.kspec)
+        } else if (K == 63 && c.knobs.kspec)
             extract_partition_kernel<2, COUNTED, B, 63><<<dim3((unsigned)xcd_grid(ftiles)), dim3(B), 0, c.stream>>>(
                 in.seq, in.seq_len, K, cmode(c, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, b1,
                 A.per_stripe, scur, send, ka, COUNTED ? ca : nullptr, &c.small->error, dsel);
@@ -2148,7 +427,7 @@ static uint64_t fused_pass_b(Ctx &c, unsigned K, bool canonical, uint32_t cmax, 
     HIP_CHECK(hipGetLastError());
     tm.mark();
     HIP_CHECK(hipStreamSynchronize(c.stream));  // `h1` / `cur` / `sel` are host memory
-    c.fused_ms = tm.ms(0, 1);
+    c.build.fused_ms = tm.ms(0, 1);
     *dh1_out = dh1;
     return acc;
 }
@@ -2156,19 +435,20 @@ static uint64_t fused_pass_b(Ctx &c, unsigned K, bool canonical, uint32_t cmax, 
 // Pass B into the speculative level-1 layout (extract_partition.hpp: spec_l1_caps_kernel) after a
 // sampled pass A (fused_pass_a with sample > 1): no exact histogram pass over every window (pass A:
 // 1.29 ms at configs[1]).  Segments of (bucket, stripe) sized from the sample with slack, each a whole
-// number of level-2 tiles; the level-2 pass reads the padded array through tvalid (c.gap1).  Returns
+// number of level-2 tiles; the level-2 pass reads the padded array through tvalid (*gap1_out).  Returns
 // the k-mer count with the exact level-1 counts in *dh1_out, or ~0 when a segment overflowed (nothing
 // the caller needs was touched: it runs the exact passes).
 static uint64_t fused_pass_b_spec(Ctx &c, unsigned K, bool canonical, const BuildInput &in, const FusedA &A,
-                                  unsigned b1, Key<1> **ka, Key<1> **kb, const uint32_t **dh1_out) {
+                                  unsigned b1, Key<1> **ka, Key<1> **kb, const uint32_t **dh1_out,
+                                  PaddedLayout *gap1_out) {
     const uint32_t nb1 = 1u << b1, S = A.stripes;
     constexpr uint32_t T2 = MsdTraits<1>::TILE;
     const uint64_t nseg = (uint64_t)nb1 * S;
     uint32_t *caps = (uint32_t *)c.ws.get(Workspace::SPEC1_CAPS, (nseg + 1) * 4);
     uint64_t *sst = (uint64_t *)c.ws.get(Workspace::SPEC1_START, (nseg + 1) * 8);
     spec_l1_caps_kernel<<<dim3(nb1), dim3(256), 0, c.stream>>>(A.rows, A.nrows, FUSED_HB, b1, S, A.rps,
-                                                               (float)A.sample_factor, T2, caps, c.spec_l1_tiny,
-                                                               c.spec_l1_slack);
+                                                               (float)A.sample_factor, T2, caps, c.knobs.spec_l1_tiny,
+                                                               c.knobs.spec_l1_slack);
     HIP_CHECK(hipGetLastError());
     {
         uint32_t ep;
@@ -2222,16 +502,15 @@ static uint64_t fused_pass_b_spec(Ctx &c, unsigned K, bool canonical, const Buil
     HIP_CHECK(hipMemcpyAsync(&povf, &c.small->spec_ovf, 4, hipMemcpyDeviceToHost, c.stream));
     HIP_CHECK(hipMemcpyAsync(&N, &c.small->total, 8, hipMemcpyDeviceToHost, c.stream));
     HIP_CHECK(hipStreamSynchronize(c.stream));
-    c.fused_ms = tm.ms(0, 1);
+    c.build.fused_ms = tm.ms(0, 1);
     if (povf) {
-        if (c.debug) fprintf(stderr, "[mtg debug] speculative level 1: a segment overflowed, exact passes\n");
+        if (c.knobs.debug) fprintf(stderr, "[mtg debug] speculative level 1: a segment overflowed, exact passes\n");
         ++c.timings.spec_fallbacks;
         return ~0ull;
     }
-    c.gap1_n = C1;
-    c.gap1_tv = tv;
+    *gap1_out = PaddedLayout{C1, tv};
     c.timings.spec_l1 = 1;
-    if (c.debug)
+    if (c.knobs.debug)
         fprintf(stderr, "[mtg debug] speculative level 1: N=%lu (sample %lu) padded %lu (%.3fx), %u stripes\n",
                 (unsigned long)N, (unsigned long)A.N, (unsigned long)C1, (double)C1 / (double)std::max<uint64_t>(N, 1), S);
     *dh1_out = dh1;
@@ -2239,11 +518,12 @@ static uint64_t fused_pass_b_spec(Ctx &c, unsigned K, bool canonical, const Buil
 }
 
 // Returns false (nothing done) when the fused path does not apply; else N, the duplication
-// estimate, and the level-1 counts in *hist1 (device) with *ka scattered.
+// estimate, and *ka scattered by the level-1 digit of *plan_out, which *rq then tells the sort: the level's
+// counts (hist1, device), the plan, and the padded layout when the speculative level 1 ran (gap1).
 template <int L2, bool COUNTED>
 static bool stage_extract_fused(Ctx &c, unsigned K, bool canonical, uint32_t cmax, const BuildInput &in,
                                 Key<L2> **ka, Key<L2> **kb, uint32_t **ca, uint32_t **cb, uint64_t *N_out,
-                                double *dup_out, const uint32_t **hist1_out, MsdPlan *plan_out) {
+                                double *dup_out, SortRequest<L2> *rq, MsdPlan *plan_out) {
     if constexpr (L2 != 1) {
         return false;
     } else {
@@ -2252,16 +532,16 @@ static bool stage_extract_fused(Ctx &c, unsigned K, bool canonical, uint32_t cma
         FusedA A;
         // the speculative level-1 layout: uncounted single builds big enough that a sample sizes the
         // segments well (the rounds and the multi-GPU collect keep the exact passes)
-        const bool spec1 = !COUNTED && K <= 32 && c.spec_l1 && npos >= c.spec_l1_min;
-        c.gap1_n = 0;
-        c.gap1_tv = nullptr;
-        c.gap1_lo = c.gap1_hi = 0;
+        const bool spec1 = !COUNTED && K <= 32 && c.knobs.spec_l1 && npos >= c.knobs.spec_l1_min;
+        rq->level1_done = true;
+        rq->force_plan = plan_out;
         if (spec1) {
-            fused_pass_a(c, K, canonical, in, &A, c.spec_l1_sample);
+            fused_pass_a(c, K, canonical, in, &A, c.knobs.spec_l1_sample);
             const MsdPlan plan = fused_plan(c, A.N, 2 * K, A.dup, true);
             if (plan.levels == 2) {
-                const uint64_t N = fused_pass_b_spec(c, K, canonical, in, A, plan.digit_end[1], ka, kb, hist1_out);
-                if (c.debug)
+                const uint64_t N = fused_pass_b_spec(c, K, canonical, in, A, plan.digit_end[1], ka, kb, &rq->hist1,
+                                                     &rq->gap1);
+                if (c.knobs.debug)
                     fprintf(stderr, "[mtg debug] fused extract (sampled) N=%lu dup=%.2f levels=%u digit1=%u\n",
                             (unsigned long)A.N, A.dup, plan.levels, plan.digit_end[1]);
                 if (N != ~0ull) {
@@ -2279,16 +559,20 @@ static bool stage_extract_fused(Ctx &c, unsigned K, bool canonical, uint32_t cma
         fused_pass_a(c, K, canonical, in, &A);
         const uint64_t N = A.N;
         const MsdPlan plan = fused_plan(c, N, 2 * K, A.dup, !COUNTED && K <= 32);
-        if (c.debug)
+        if (c.knobs.debug)
             fprintf(stderr, "[mtg debug] fused extract N=%lu dup=%.2f levels=%u digit1=%u\n", (unsigned long)N, A.dup,
                     plan.levels, plan.levels ? plan.digit_end[1] : 0);
-        if (!plan.levels) return false;  // nothing to partition: the plain extraction path
+        if (!plan.levels) {  // nothing to partition: the plain extraction path
+            rq->level1_done = false;
+            rq->force_plan = nullptr;
+            return false;
+        }
         const unsigned b1 = plan.digit_end[1];
         *ka = (Key<1> *)c.ws.get(Workspace::KA, std::max<uint64_t>(N, 1) * 8);
         *kb = (Key<1> *)c.ws.get(Workspace::KB, std::max<uint64_t>(N, 1) * 8);
         *ca = COUNTED ? (uint32_t *)c.ws.get(Workspace::CA, std::max<uint64_t>(N, 1) * 4) : nullptr;
         *cb = COUNTED ? (uint32_t *)c.ws.get(Workspace::CB, std::max<uint64_t>(N, 1) * 4) : nullptr;
-        fused_pass_b<1, COUNTED>(c, K, canonical, cmax, in, A, b1, nullptr, *ka, COUNTED ? *ca : nullptr, hist1_out);
+        fused_pass_b<1, COUNTED>(c, K, canonical, cmax, in, A, b1, nullptr, *ka, COUNTED ? *ca : nullptr, &rq->hist1);
         c.timings.n_positions = npos;
         c.timings.n_extracted = N;
         *N_out = N;
@@ -2302,13 +586,12 @@ static bool stage_extract_fused(Ctx &c, unsigned K, bool canonical, uint32_t cma
 // expected number of copies per distinct key (plans the MSD depth only).
 template <int L2, bool COUNTED>
 static uint64_t stage_collect(Ctx &c, unsigned K, uint32_t cmax, Key<L2> **ka, Key<L2> **kb,
-                              uint32_t **ca, uint32_t **cb, uint64_t N, double dup, bool track,
-                              const uint32_t *hist1 = nullptr, const MsdPlan *plan = nullptr) {
-    // hist1 != nullptr: *ka is already scattered by the level-1 digit (stage_extract_fused)
+                              uint32_t **ca, uint32_t **cb, uint64_t N, double dup, SortRequest<L2> &rq) {
+    // rq.hist1 != nullptr: *ka is already scattered by the level-1 digit (stage_extract_fused), to
+    // rq.force_plan
     uint64_t U = 0;
-    if (!hist1) c.gap1_n = 0, c.gap1_tv = nullptr, c.gap1_lo = c.gap1_hi = 0;
-    if (c.use_lsd) {
-        radix_sort<L2, COUNTED>(c, ka, kb, ca, cb, N, 2 * K, track);
+    if (c.knobs.use_lsd) {
+        radix_sort<L2, COUNTED>(c, ka, kb, ca, cb, N, 2 * K, rq.track_partition);
         reset_small(c);
         if (N) {
             const uint64_t tiles = ceil_div(N, 2048);
@@ -2332,11 +615,8 @@ static uint64_t stage_collect(Ctx &c, unsigned K, uint32_t cmax, Key<L2> **ka, K
         std::swap(*ka, *kb);
         std::swap(*ca, *cb);
     } else {
-        c.track_partition = track;
         if (dup <= 0) dup = estimate_dup<L2>(c, *ka, N, 8.0);
-        U = msd_sort_unique<L2, COUNTED>(c, ka, kb, ca, cb, N, 2 * K, cmax, dup, hist1, false, nullptr,
-                                         hist1 != nullptr, nullptr, hist1 ? plan : nullptr);
-        c.track_partition = false;
+        U = msd_sort_unique<L2, COUNTED>(c, ka, kb, ca, cb, N, 2 * K, cmax, dup, rq);
     }
     return U;
 }
@@ -2362,16 +642,16 @@ template <int L2, bool COUNTED>
 static uint32_t plan_ranges(Ctx &c, unsigned K, bool canonical, const BuildInput &in) {
     const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
     if (K < RB_CHARS + 1) return 1;  // at most 4^4 distinct k-mers: never worth a range
-    if (c.force_ranges) return c.force_ranges;
+    if (c.knobs.force_ranges) return c.knobs.force_ranges;
     const double per_key = (double)sizeof(Key<L2>) + (COUNTED ? 4.0 : 0.0);
-    double budget = c.mem_budget;
+    double budget = c.params.mem_budget;
     if (budget <= 0) {
         size_t fr = 0, tot = 0;
         HIP_CHECK(hipMemGetInfo(&fr, &tot));
         budget = 0.9 * ((double)fr + (double)c.ws.held());
     }
     // single pass: KA + KB over every window, then the real edges, rc and dummy buffers
-    if ((double)npos * per_key * 2.5 <= budget && !c.disk) return 1;
+    if ((double)npos * per_key * 2.5 <= budget && !c.params.disk) return 1;
     const double keys = (double)npos * (canonical ? 2.0 : 1.0);
     uint32_t P = (uint32_t)std::ceil(keys * per_key * 2.0 / (0.4 * budget));
     P = std::max<uint32_t>(P, (uint32_t)std::ceil(keys / 2.0e9));  // <= 2e9 keys per range
@@ -2441,9 +721,9 @@ static uint64_t collect_ranges(Ctx &c, unsigned K, bool canonical, uint32_t cmax
         // keys were spread over all of it
         const double spread = (double)RB_BINS / (double)(hi - lo);
         const double dup = estimate_dup<L2>(c, ka, N, 8.0) / spread;
-        c.track_partition = j == 0;  // the roofline's partition pass: the first range's first level
-        const uint64_t U = msd_sort_unique<L2, COUNTED>(c, &ka, &kb, &ca, &cb, N, 2 * K, cmax, dup);
-        c.track_partition = false;
+        SortRequest<L2> rq;
+        rq.track_partition = j == 0;  // the roofline's partition pass: the first range's first level
+        const uint64_t U = msd_sort_unique<L2, COUNTED>(c, &ka, &kb, &ca, &cb, N, 2 * K, cmax, dup, rq);
         if (off + U > cap) {
             // first range: size the real edges from its distinct ratio (+25 %); later growth keeps
             // what is already appended
@@ -2486,7 +766,7 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     // pass B on 256-thread tiles; the later levels are the MSD sort's exact ones
     using K2 = Key<L>;
     const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
-    if (c.range_scan || c.disk || !fused_applies(c, K, npos, L == 1 ? 32 : 64)) return false;
+    if (c.knobs.range_scan || c.params.disk || !fused_applies(c, K, npos, L == 1 ? 32 : 64)) return false;
     // a previous build's stage buffers would crowd out this build's rounds: they go now (and are
     // allocated again at the sizes this build needs)
     Tracer tr{c, 0};
@@ -2513,8 +793,8 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     for (uint32_t i = 0; i < (1u << FUSED_HB); ++i) h1[i >> (FUSED_HB - b1)] += A.h[i];
     // rounds: the later stages hold ~5 keys of 8 B per distinct canonical k-mer (the canonical set, the
     // real edges, the rc sort's two buffers) plus the rows; a round holds its keys twice (+ counts)
-    uint32_t R = c.force_ranges;
-    double budget = c.mem_budget;
+    uint32_t R = c.knobs.force_ranges;
+    double budget = c.params.mem_budget;
     if (budget <= 0) {
         size_t fr = 0, tot = 0;
         HIP_CHECK(hipMemGetInfo(&fr, &tot));
@@ -2549,7 +829,7 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     // learned to carve pieces off its kept blocks, Workspace::take_cached)
     bool one_b = false;
     // (u128, configs[2]: both rounds' keys, 141 GB, beside KB and the canonical set -- ~255 of the 309 GB)
-    if (R == 2 && c.rounds_one_b && ((L == 1 && !COUNTED && K <= 32) || fast2_applies<L, COUNTED>(c, K, canonical))) {
+    if (R == 2 && c.knobs.rounds_one_b && ((L == 1 && !COUNTED && K <= 32) || fast2_applies<L, COUNTED>(c, K, canonical))) {
         const double kb = (double)sizeof(K2);
         const double need = ((double)N + (double)nmax) * kb + u_est * 1.25 * kb + (double)(1ull << 30);
         one_b = need <= budget;
@@ -2560,11 +840,8 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     // needs no third round-sized block and its histogram pass goes (configs[3]'s share: levels 2 and 3
     // were both exact, a 60 GB read each per round)
     uint64_t ka_keys = one_b ? nr[0] : nmax;
-    struct SpareGuard {  // never left set past this function (a thrown build included)
-        Ctx &c;
-        ~SpareGuard() { c.spec_into = nullptr, c.spec_into_bytes = 0, c.spec_mid_into = nullptr, c.spec_mid_bytes = 0; }
-    } spare_guard{c};
-    if (L == 1 && !COUNTED && plan.levels == 3 && c.spec3 && c.spec_final && c.spec_inplace && !c.use_lsd) {
+    SortRequest<L> spare;  // the spare buffers every round's sort is offered (spec_into, spec_mid_into)
+    if (L == 1 && !COUNTED && plan.levels == 3 && c.knobs.spec3 && c.knobs.spec_final && c.knobs.spec_inplace && !c.knobs.use_lsd) {
         double fmax = 0;
         for (uint32_t r = 0; r < R; ++r) fmax = std::max(fmax, (double)(bb[r + 1] - bb[r]) / (double)nb1);
         const double cap = (1.2 * (double)nmax + 512.0 * (double)(1ull << plan.digit_end[3]) * fmax) * 1.05 + 65536.0;
@@ -2574,12 +851,12 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
         if (cap > (double)ka_keys && need <= budget) ka_keys = (uint64_t)cap;
     }
     K2 *ka = (K2 *)c.ws.get(Workspace::KA, ka_keys * sizeof(K2));
-    if (L == 1 && ka_keys > (one_b ? nr[0] : nmax)) c.spec_into = ka, c.spec_into_bytes = ka_keys * sizeof(K2);
+    if (L == 1 && ka_keys > (one_b ? nr[0] : nmax)) spare.spec_into = ka, spare.spec_into_bytes = ka_keys * sizeof(K2);
     K2 *ka2 = one_b ? (K2 *)c.ws.get(Workspace::KA2, std::max<uint64_t>(nr[1], 1) * sizeof(K2)) : nullptr;
     // ... and the speculative middle level (spec_mid_level) partitions into KB: sized for its tile-aligned
     // slack buckets -- 1.2 n + 512 keys and up to one tile a bucket -- when that fits too
     uint64_t kb_keys = nmax;
-    if (L == 1 && c.spec_into && c.spec_mid && plan.levels == 3) {
+    if (L == 1 && spare.spec_into && c.knobs.spec_mid && plan.levels == 3) {
         double fmax = 0;
         for (uint32_t r = 0; r < R; ++r) fmax = std::max(fmax, (double)(bb[r + 1] - bb[r]) / (double)nb1);
         const double mcap = 1.2 * (double)nmax * 1.05 +
@@ -2590,7 +867,7 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
         if (need <= budget) kb_keys = (uint64_t)mcap;
     }
     K2 *kb = (K2 *)c.ws.get(Workspace::KB, kb_keys * sizeof(K2));
-    if (kb_keys > nmax) c.spec_mid_into = kb, c.spec_mid_bytes = kb_keys * sizeof(K2);
+    if (kb_keys > nmax) spare.spec_mid_into = kb, spare.spec_mid_bytes = kb_keys * sizeof(K2);
     uint32_t *ca = COUNTED ? (uint32_t *)c.ws.get(Workspace::CA, nmax * 4) : nullptr;
     uint32_t *cb = COUNTED ? (uint32_t *)c.ws.get(Workspace::CB, nmax * 4) : nullptr;
     tr("rounds: buffers", R, nmax);
@@ -2610,7 +887,7 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
         tr("rounds: pass B (both rounds)", R, n);
     }
     std::vector<uint32_t> h1r(nb1);  // one_b: a round's level-1 counts (zero outside its buckets)
-    if (c.debug)
+    if (c.knobs.debug)
         fprintf(stderr, "[mtg debug] canonical rounds: N=%lu dup=%.2f levels=%u digit1=%u rounds=%u largest=%lu\n",
                 (unsigned long)N, A.dup, plan.levels, b1, R, (unsigned long)nmax);
     c.timings.n_positions = npos;
@@ -2622,24 +899,20 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     *outc = nullptr;
     bool first = true;
     // the canonical set sized from pass A's duplication estimate up front, so that every round's final
-    // gather writes its distinct keys straight into it (c.sort_out) instead of into the round buffer and a
+    // gather writes its distinct keys straight into it (SortRequest::out) instead of into the round buffer and a
     // copy after (a 19 GB copy per configs[3] round); a round that finds more falls back to that copy
     if (R > 1 && !COUNTED) {
         cap = (uint64_t)u_est + 65536;
         *out = (K2 *)c.ws.get(Workspace::CANON, cap * sizeof(K2));
     }
-    struct SortOutGuard {
-        Ctx &c;
-        ~SortOutGuard() { c.sort_out = nullptr, c.sort_out_vals = nullptr, c.sort_out_cap = ~0ull, c.ridx = Ctx::RoundIndex{}; }
-    } sort_out_guard{c};
     // the rc stage reads the canonical set through a bucket index over the rc sort's final bits (its plan
     // for the set's size, estimated here from pass A's duplication): each round's speculative gather writes
-    // its buckets' entries (Ctx::ridx) instead of a bucket_index pass over the whole set after the rounds
+    // its buckets' entries (SortRequest::ridx) instead of a bucket_index pass over the whole set after the rounds
     // (5.6 ms at configs[3]'s share); a round that takes another path leaves it to that pass
     unsigned fb_est = 0;
     uint64_t *rgi = nullptr;
     bool rgi_ok = false;
-    if (canonical && !COUNTED && c.round_index) {
+    if (canonical && !COUNTED && c.knobs.round_index) {
         const MsdPlan rp = rc_plan<L>(c, std::max<uint64_t>(1, (uint64_t)((double)N / A.dup)), 2 * K);
         fb_est = rp.levels ? rp.digit_end[rp.levels] : 0;
         if (fb_est >= b1 && fb_est <= 26) {
@@ -2676,26 +949,26 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
             if (n != nr[r]) throw std::runtime_error("a collect round's k-mers differ from its histogram");
             tr("rounds: pass B", r, n);
         }
-        c.track_partition = first;  // the roofline's partition pass: the first round's level 2
+        SortRequest<L> rq = spare;
+        rq.hist1 = dh1;
+        rq.level1_done = true;
+        rq.track_partition = first;  // the roofline's partition pass: the first round's level 2
         MsdPlan rplan = plan;
-        if (L == 1 && c.round_bits && plan.levels >= 2) {
-            // keys per final bucket in this round against the whole input's average (Ctx::round_bits)
+        if (L == 1 && c.knobs.round_bits && plan.levels >= 2) {
+            // keys per final bucket in this round against the whole input's average (Knobs::round_bits)
             const unsigned T = plan.digit_end[plan.levels], bp = plan.digit_end[plan.levels - 1];
             const double nbk = (double)(bb[r + 1] - bb[r]) * (double)(1ull << (T - b1));
             const double rho = ((double)n / nbk) / ((double)N / (double)(1ull << T));
             if (rho < 0.75 && T >= bp + 2) rplan.digit_end[plan.levels] = T - 1;
         }
         if (*out && off < cap && (!COUNTED || *outc)) {
-            c.sort_out = *out + off, c.sort_out_cap = cap - off;
-            c.sort_out_vals = COUNTED ? *outc + off : nullptr;  // (the counts travel with their keys)
+            rq.out = *out + off, rq.out_cap = cap - off;
+            rq.out_vals = COUNTED ? *outc + off : nullptr;  // (the counts travel with their keys)
         }
-        if (rgi_ok) c.ridx = Ctx::RoundIndex{rgi, fb_est, off, bb[r] << (fb_est - b1), bb[r + 1] << (fb_est - b1), false};
-        const uint64_t U = msd_sort_unique<L, COUNTED>(c, &xa, &xb, &xac, &xbc, n, 2 * K, cmax, A.dup, dh1, false,
-                                                       nullptr, true, nullptr, &rplan);
-        rgi_ok = rgi_ok && c.ridx.written;
-        c.ridx = Ctx::RoundIndex{};
-        c.sort_out = nullptr, c.sort_out_vals = nullptr, c.sort_out_cap = ~0ull;
-        c.track_partition = false;
+        if (rgi_ok) rq.ridx = RoundIndex{rgi, fb_est, off, bb[r] << (fb_est - b1), bb[r + 1] << (fb_est - b1)};
+        rq.force_plan = &rplan;
+        const uint64_t U = msd_sort_unique<L, COUNTED>(c, &xa, &xb, &xac, &xbc, n, 2 * K, cmax, A.dup, rq);
+        rgi_ok = rgi_ok && rq.ridx_written;
         first = false;
         tr("rounds: sort", r, U);
         if (off + U > cap) {
@@ -2712,7 +985,7 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
             if (COUNTED) HIP_CHECK(hipMemcpyAsync(*outc + off, xac, U * 4, hipMemcpyDeviceToDevice, c.stream));
         }
         off += U;
-        if (c.debug)
+        if (c.knobs.debug)
             fprintf(stderr, "[mtg debug]   round %u: buckets [%lu, %lu) n=%lu -> %lu distinct\n", r,
                     (unsigned long)bb[r], (unsigned long)bb[r + 1], (unsigned long)n, (unsigned long)U);
     }
@@ -2721,7 +994,6 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
         if (COUNTED) *outc = (uint32_t *)c.ws.get(Workspace::CANONC, 4);
     }
     debug_check_sorted(c, "canonical rounds", *out, off);
-    c.spec_into = nullptr, c.spec_into_bytes = 0, c.spec_mid_into = nullptr, c.spec_mid_bytes = 0;
     // the round buffers (sized for the largest round) go; the rc stage takes KB and SPEC_A again at
     // its own size
     for (auto sl : {Workspace::KA, Workspace::KA2, Workspace::CA, Workspace::KB, Workspace::CB, Workspace::SPEC_A,
@@ -2729,7 +1001,6 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
         c.ws.release(sl);
     // the fused rc merge reads the canonical keys through their bucket index over the rc sort's final
     // bits (a one-pass build gets it from its own sort's groups)
-    c.gidx = Ctx::GroupIndex{};
     if (canonical && off && !COUNTED) {
         const MsdPlan rp = rc_plan<L>(c, off, 2 * K);
         const unsigned fb = rp.levels ? rp.digit_end[rp.levels] : 0;
@@ -2739,12 +1010,12 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
             if (rgi_ok && fb == fb_est && gi == rgi) {  // written by the rounds' gathers: its two end entries
                 fill_u64_kernel<<<dim3(1), dim3(256), 0, c.stream>>>(gi, nb, nb + 2, off);
                 HIP_CHECK(hipGetLastError());
-                if (c.debug) fprintf(stderr, "[mtg debug] canonical rounds: bucket index from the rounds' gathers\n");
+                if (c.knobs.debug) fprintf(stderr, "[mtg debug] canonical rounds: bucket index from the rounds' gathers\n");
             } else {
                 bucket_index<L>(c, *out, off, 2 * K - fb, nb, gi);
                 HIP_CHECK(hipMemcpyAsync(gi + nb + 1, gi + nb, 8, hipMemcpyDeviceToDevice, c.stream));
             }
-            c.gidx = Ctx::GroupIndex{*out, off, fb, 2 * K, gi};
+            c.build.gidx = GroupIndex{*out, off, fb, 2 * K, gi};
 
         }
     }
@@ -2767,11 +1038,11 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
     uint32_t *rc_hist = nullptr;
     bool rc_level1 = false;  // buf already partitioned by the rc sort's level-1 digit
     // the fused merge's plan (rc_plan: u128 merge groups twice as full); the plain sort plans its own
-    const bool own_plan = rm && L2 == 2 && c.rc_wide;
+    const bool own_plan = rm && L2 == 2 && c.knobs.rc_wide;
     const MsdPlan rcp = own_plan ? rc_plan<L2>(c, U, 2 * K) : MsdPlan{};
     if (K & 1) {
         unsigned rc_hist_bits = 0;
-        if (!c.use_lsd && sort) {
+        if (!c.knobs.use_lsd && sort) {
             const MsdPlan plan = own_plan ? rcp : msd_plan<L2>(c, U, 2 * K, 1.0);
             if (plan.levels) {
                 rc_hist_bits = plan.digit_end[1];
@@ -2781,19 +1052,19 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
         }
         bool done = false;
         if constexpr (!COUNTED) {
-            if (c.gap.valid && c.gap.dst == (const void *)ka && sort) {
-                // the canonical set still in its speculative buckets (Ctx::gap): read it there
-                const bool fuse = c.rc_fuse && rc_hist && rc_hist_bits <= 9 && c.gap1_n == 0 && U;
+            if (c.build.gap.valid && c.build.gap.dst == (const void *)ka && sort) {
+                // the canonical set still in its speculative buckets (BuildState::gap): read it there
+                const bool fuse = c.knobs.rc_fuse && rc_hist && rc_hist_bits <= 9 && U;
                 const uint64_t tiles = ceil_div(U, RcPartTraits<L2>::TILE);
                 // (fuse: the histogram only)
-                rc_map_gapped_kernel<L2><<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(c.gap.nb, 16), 16384))),
-                                           dim3(256), 0, c.stream>>>((const K2 *)c.gap.keys, c.gap.bstart, c.gap.ustart,
-                                                                     c.gap.nb, fuse ? nullptr : buf, K, rc_hist, rc_hist_bits);
+                rc_map_gapped_kernel<L2><<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(c.build.gap.nb, 16), 16384))),
+                                           dim3(256), 0, c.stream>>>((const K2 *)c.build.gap.keys, c.build.gap.bstart, c.build.gap.ustart,
+                                                                     c.build.gap.nb, fuse ? nullptr : buf, K, rc_hist, rc_hist_bits);
                 HIP_CHECK(hipGetLastError());
                 if (fuse) {
                     uint64_t *tile_g = (uint64_t *)c.ws.get(Workspace::RC_TILEG, tiles * 8);
-                    rc_tile_bucket_kernel<<<dim3((unsigned)ceil_div(c.gap.nb, 256)), dim3(256), 0, c.stream>>>(
-                        c.gap.ustart, c.gap.nb, RcPartTraits<L2>::TILE, tile_g);
+                    rc_tile_bucket_kernel<<<dim3((unsigned)ceil_div(c.build.gap.nb, 256)), dim3(256), 0, c.stream>>>(
+                        c.build.gap.ustart, c.build.gap.nb, RcPartTraits<L2>::TILE, tile_g);
                     HIP_CHECK(hipGetLastError());
                     // the histogram above gives the level-1 bucket starts; the rc keys are then written
                     // straight into their level-1 buckets (rc_partition_gapped_kernel)
@@ -2808,7 +1079,7 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
                     HIP_CHECK(hipGetLastError());
                     HIP_CHECK(hipMemcpyAsync(cur, st, nbk * 8, hipMemcpyDeviceToDevice, c.stream));
                     rc_partition_gapped_kernel<L2><<<dim3((unsigned)xcd_grid(tiles)), dim3(512), 0, c.stream>>>(
-                        (const K2 *)c.gap.keys, c.gap.bstart, c.gap.ustart, tile_g, c.gap.nb, U, K, rc_hist_bits, cur,
+                        (const K2 *)c.build.gap.keys, c.build.gap.bstart, c.build.gap.ustart, tile_g, c.build.gap.nb, U, K, rc_hist_bits, cur,
                         buf);
                     HIP_CHECK(hipGetLastError());
                     rc_level1 = true;
@@ -2841,9 +1112,16 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
     }
     K2 *ra = buf, *rb = (K2 *)c.ws.get(Workspace::RC_ALT, Urc * sizeof(K2));
     uint32_t *rca = bufc, *rcb = COUNTED ? (uint32_t *)c.ws.get(Workspace::RC_ALTC, Urc * 4) : nullptr;
-    if (c.use_lsd) radix_sort<L2, COUNTED>(c, &ra, &rb, &rca, &rcb, Urc, 2 * K, false);
-    else Urc = msd_sort_unique<L2, COUNTED>(c, &ra, &rb, &rca, &rcb, Urc, 2 * K, cmax, 1.0, rc_hist, true, nullptr,
-                                            rc_level1, rm, own_plan && rcp.levels ? &rcp : nullptr);
+    if (c.knobs.use_lsd) radix_sort<L2, COUNTED>(c, &ra, &rb, &rca, &rcb, Urc, 2 * K, false);
+    else {
+        SortRequest<L2> rq;
+        rq.hist1 = rc_hist;
+        rq.distinct = true;
+        rq.level1_done = rc_level1;
+        rq.rm = rm;
+        rq.force_plan = own_plan && rcp.levels ? &rcp : nullptr;
+        Urc = msd_sort_unique<L2, COUNTED>(c, &ra, &rb, &rca, &rcb, Urc, 2 * K, cmax, 1.0, rq);
+    }
     *rk = ra;
     *rkc = rca;
     return Urc;
@@ -2898,7 +1176,7 @@ static uint64_t sort_unique_dummies(Ctx &c, unsigned K, Key<L3> *da, Key<L3> *db
     uint32_t *nv = nullptr;
     const unsigned kb = K - 1;
     const int LR = dummy_rank_limbs(kb);
-    if (c.dummy_ranks && kb >= 1 && LR && (LR == 1 || L3 >= 2) && Draw) {
+    if (c.knobs.dummy_ranks && kb >= 1 && LR && (LR == 1 || L3 >= 2) && Draw) {
         HIP_CHECK(hipMemsetAsync(&c.small->bad_dummy, 0, 4, c.stream));
         const unsigned g = (unsigned)std::min<uint64_t>(ceil_div(Draw, 256), 16384);
         if (LR == 1)
@@ -2913,7 +1191,7 @@ static uint64_t sort_unique_dummies(Ctx &c, unsigned K, Key<L3> *da, Key<L3> *db
             if (LR == 1) return sort_unique_dummy_ranks<L3, 1>(c, kb, da, db, (Key<1> *)db, Draw, dk);
             if constexpr (L3 >= 2) return sort_unique_dummy_ranks<L3, 2>(c, kb, da, db, (Key<2> *)db, Draw, dk);
         }
-        if (c.debug) fprintf(stderr, "[mtg debug] dummy keys outside the rank shape: lifted sort\n");
+        if (c.knobs.debug) fprintf(stderr, "[mtg debug] dummy keys outside the rank shape: lifted sort\n");
     }
     {
         radix_sort<L3, false>(c, &da, &db, &nv, &nv, Draw, 3 * K, false);
@@ -2931,22 +1209,6 @@ static uint64_t sort_unique_dummies(Ctx &c, unsigned K, Key<L3> *da, Key<L3> *db
     return D;
 }
 
-// remember the bucket index over the real edges for the split emit's dummy ranks
-static void note_bucket_index(Ctx &c, const void *keys, uint64_t n, const uint64_t *start, unsigned shift) {
-    c.bidx_keys = keys;
-    c.bidx_n = n;
-    c.bidx = start;
-    c.bidx_shift = shift;
-    c.bidx_gen = c.ws.generation(Workspace::BUCKETS);
-}
-
-// the remembered bucket index still describes keys[0..n): the same array and count, and its entries still
-// in the BUCKETS slot it was written to (a released or regrown slot may now hold another stage's data)
-static bool bidx_valid(const Ctx &c, const void *keys, uint64_t n) {
-    return c.bidx && c.bidx_keys == keys && c.bidx_n == n && (const void *)c.bidx == c.ws.peek(Workspace::BUCKETS) &&
-           c.bidx_gen == c.ws.generation(Workspace::BUCKETS);
-}
-
 // K5/K6 on one device: dummy sinks and sources (all levels) of the sorted real edges ka[0..R)
 template <int L2, int L3>
 static uint64_t stage_dummies_local(Ctx &c, unsigned K, const Key<L2> *ka, uint64_t R, Key<L3> **dk) {
@@ -2956,7 +1218,7 @@ static uint64_t stage_dummies_local(Ctx &c, unsigned K, const Key<L2> *ka, uint6
     const unsigned bshift = 2 * K - B;
     const uint64_t nb = 1ull << B;
     uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::BUCKETS, (nb + 2) * 8);
-    if (!(bidx_valid(c, ka, R) && c.bidx_shift == bshift && c.bidx == bstart)) {
+    if (!(bidx_valid(c, ka, R) && c.build.bidx_shift == bshift && c.build.bidx == bstart)) {
         const uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(R + 1, 256), 8192));
         bucket_index_kernel<L2><<<dim3((unsigned)g), dim3(256), 0, c.stream>>>(ka, R, bshift, nb, bstart);
         HIP_CHECK(hipGetLastError());
@@ -2970,7 +1232,7 @@ static uint64_t stage_dummies_local(Ctx &c, unsigned K, const Key<L2> *ka, uint6
     uint64_t Draw = 0;
     // the dense-rank path writes the source levels with <= DUMMY_BITMAP_M real chars as bits of a bitmap
     // (dummy_write_kernel), so the count pass counts kbig levels per source
-    const bool bitmap_path = L2 == 1 && c.dummy_ranks && c.dummy_bitmap && k >= 1 && k <= 30;
+    const bool bitmap_path = L2 == 1 && c.knobs.dummy_ranks && c.knobs.dummy_bitmap && k >= 1 && k <= 30;
     const unsigned ks = std::min<unsigned>(k, DUMMY_BITMAP_M + 1), kbig = bitmap_path ? k - ks : k;
     if (R) {
         HIP_CHECK(hipMemsetAsync(in_flag, 0, R, c.stream));
@@ -3008,7 +1270,7 @@ static uint64_t stage_dummies_local(Ctx &c, unsigned K, const Key<L2> *ka, uint6
                                         dim3(256), 0, c.stream>>>(bm, nwords, k, ks, (uint64_t *)da, &c.small->total);
             HIP_CHECK(hipGetLastError());
             const uint64_t Dall = read_u64(c, &c.small->total);  // (also orders the copy of the host local)
-            if (c.debug)
+            if (c.knobs.debug)
                 fprintf(stderr, "[mtg debug] dummies: %lu written + %lu from the bitmap (%u levels per source)\n",
                         (unsigned long)Draw, (unsigned long)(Dall - Draw), ks);
             if (!Dall) return 0;
@@ -3019,7 +1281,7 @@ static uint64_t stage_dummies_local(Ctx &c, unsigned K, const Key<L2> *ka, uint6
     K3 *da = (K3 *)c.ws.get(Workspace::DA, Draw * sizeof(K3));
     K3 *db = (K3 *)c.ws.get(Workspace::DB, Draw * sizeof(K3));
     if constexpr (L2 == 1) {
-        if (c.dummy_ranks && k <= 30) {  // written as dense ranks: no lifted keys until the decode
+        if (c.knobs.dummy_ranks && k <= 30) {  // written as dense ranks: no lifted keys until the decode
             dummy_write_kernel<L2, L3, true><<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(ka, flags, in_flag,
                                                                                                   R, K, toff, da);
             HIP_CHECK(hipGetLastError());
@@ -3027,7 +1289,7 @@ static uint64_t stage_dummies_local(Ctx &c, unsigned K, const Key<L2> *ka, uint6
         }
     }
     if constexpr (L2 <= 2 && L3 >= 2) {
-        if (c.dummy_ranks && dummy_rank_limbs(k) == 2) {  // 30 < k <= 62: dense u128 ranks (configs[2]: k = 62)
+        if (c.knobs.dummy_ranks && dummy_rank_limbs(k) == 2) {  // 30 < k <= 62: dense u128 ranks (configs[2]: k = 62)
             dummy_write_kernel<L2, L3, true, 2><<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(ka, flags, in_flag,
                                                                                                      R, K, toff, da);
             HIP_CHECK(hipGetLastError());
@@ -3038,76 +1300,6 @@ static uint64_t stage_dummies_local(Ctx &c, unsigned K, const Key<L2> *ka, uint6
                                                                                     toff, da);
     HIP_CHECK(hipGetLastError());
     return sort_unique_dummies<L3>(c, K, da, db, Draw, dk);
-}
-
-template <int L3, bool COUNTED>
-static void emit_stream(Ctx &c, unsigned k, uint32_t wmax, const Key<L3> *sk, const uint32_t *sc, uint64_t M,
-                        uint64_t R, BuildOutput *out);
-
-// K7 + K8: lift + merge the real edges with the sorted dummies (behind the main dummy row when
-// `root`), then W / last / F / weights.  Rows go to out[1..]; out row 0 is the leading row.
-template <int L2, int L3, bool COUNTED>
-static void stage_merge_emit(Ctx &c, EventTimer &tm, int *ev_merge, unsigned k, unsigned bits,
-                             const Key<L2> *real, const uint32_t *realc, uint64_t R, const Key<L3> *dk,
-                             uint64_t D, bool root, BuildOutput *out) {
-    using K3 = Key<L3>;
-    const unsigned K = k + 1;
-    const uint32_t wmax = bits >= 32 ? 0xFFFFFFFFu : (uint32_t)((1ull << bits) - 1);
-    const uint64_t M = (root ? 1 : 0) + R + D;
-    if (c.fused_emit && !c.emit_slow && M) {
-        // K7 + K8 without the merged stream (split_emit_kernel): the dummies' output rows from
-        // their ranks in A, then one pass over the output rows; a violated premise or a redundant
-        // sink falls through to the exact unfused path below
-        using SE = SplitEmitTraits<L2>;
-        const uint64_t nout = M + 1;
-        uint8_t *W = (uint8_t *)c.ws.get(Workspace::OW, nout);
-        uint8_t *last = (uint8_t *)c.ws.get(Workspace::OLAST, nout);
-        uint32_t *weights = COUNTED ? (uint32_t *)c.ws.get(Workspace::OWEIGHTS, nout * 4) : nullptr;
-        uint64_t *pos = (uint64_t *)c.ws.get(Workspace::DPOS, D * 8);
-        uint8_t *wl = (uint8_t *)c.ws.get(Workspace::DWL, D);
-        const uint64_t ntiles = ceil_div(nout, SE::TILE);
-        uint64_t *jsplit = (uint64_t *)c.ws.get(Workspace::SPLITS, (ntiles + 1) * 8);
-        reset_small(c);
-        if (D) {
-            const bool idx = bidx_valid(c, real, R);
-            dummy_rank_kernel<L2, L3><<<dim3((unsigned)ceil_div(D, 256)), dim3(256), 0, c.stream>>>(
-                real, R, dk, D, K, idx ? c.bidx : nullptr, c.bidx_shift, root ? 2 : 1, pos, wl,
-                &c.small->skip, &c.small->root_same);
-            HIP_CHECK(hipGetLastError());
-        }
-        split_points_kernel<SE::TILE><<<dim3((unsigned)ceil_div(ntiles + 1, 256)), dim3(256), 0, c.stream>>>(
-            pos, D, ntiles, jsplit);
-        HIP_CHECK(hipGetLastError());
-        split_emit_kernel<L2, COUNTED><<<dim3((unsigned)ntiles), dim3(SE::BLOCK), 0, c.stream>>>(
-            real, realc, R, pos, wl, jsplit, nout, root ? 1 : 0, &c.small->root_same, wmax, W, last, weights);
-        HIP_CHECK(hipGetLastError());
-        f_bounds_split_kernel<L3, L2><<<1, 64, 0, c.stream>>>(real, R, dk, D, K, root ? 1 : 0, c.small->fhist);
-        HIP_CHECK(hipGetLastError());
-        *ev_merge = tm.mark();
-        Small h;
-        HIP_CHECK(hipMemcpyAsync(&h, c.small, sizeof(Small), hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        if (!h.skip) {
-            for (int ch = 0; ch < 5; ++ch) out->F[ch] = h.fhist[ch];
-            out->W = W;
-            out->last = last;
-            out->weights = weights;
-            out->n = nout;
-            out->n_real = R;
-            out->n_dummy = M - R;
-            return;
-        }
-    }
-    K3 *sk = (K3 *)c.ws.get(Workspace::STREAM, M * sizeof(K3));
-    uint32_t *sc = COUNTED ? (uint32_t *)c.ws.get(Workspace::SCOUNT, M * 4) : nullptr;
-    if (root) {
-        set_root_row_kernel<<<1, 1, 0, c.stream>>>((uint64_t *)sk, L3, COUNTED ? sc : nullptr);
-        HIP_CHECK(hipGetLastError());
-    }
-    merge_sorted<L3, L2, true, COUNTED, false>(c, real, realc, R, dk, nullptr, D, K, sk, sc, root ? 1 : 0);
-    debug_check_sorted(c, "merged stream", sk, M);
-    *ev_merge = tm.mark();
-    emit_stream<L3, COUNTED>(c, k, wmax, sk, sc, M, R, out);
 }
 
 // K8 over a sorted lifted stream sk[0..M) (+ counts): initialize_chunk (boss_chunk.cpp:32-133),
@@ -3123,7 +1315,7 @@ static void emit_stream(Ctx &c, unsigned k, uint32_t wmax, const Key<L3> *sk, co
     if (COUNTED) HIP_CHECK(hipMemsetAsync(weights, 0, 4, c.stream));
     reset_small(c);
     uint64_t rows = M;
-    bool slow = c.emit_slow;
+    bool slow = c.knobs.emit_slow;
     if (!slow && M) {
         emit_fast_kernel<L3, COUNTED><<<dim3((unsigned)ceil_div(M + 1, 256 * 8)), dim3(256), 0, c.stream>>>(
             sk, sc, M, k, wmax, W, last, weights, &c.small->skip);
@@ -3165,6 +1357,72 @@ static void emit_stream(Ctx &c, unsigned k, uint32_t wmax, const Key<L3> *sk, co
     out->n_dummy = rows - R;
 }
 
+// K7 + K8: lift + merge the real edges with the sorted dummies (behind the main dummy row when
+// `root`), then W / last / F / weights.  Rows go to out[1..]; out row 0 is the leading row.
+template <int L2, int L3, bool COUNTED>
+static void stage_merge_emit(Ctx &c, EventTimer &tm, int *ev_merge, unsigned k, unsigned bits,
+                             const Key<L2> *real, const uint32_t *realc, uint64_t R, const Key<L3> *dk,
+                             uint64_t D, bool root, BuildOutput *out) {
+    using K3 = Key<L3>;
+    const unsigned K = k + 1;
+    const uint32_t wmax = bits >= 32 ? 0xFFFFFFFFu : (uint32_t)((1ull << bits) - 1);
+    const uint64_t M = (root ? 1 : 0) + R + D;
+    if (c.knobs.fused_emit && !c.knobs.emit_slow && M) {
+        // K7 + K8 without the merged stream (split_emit_kernel): the dummies' output rows from
+        // their ranks in A, then one pass over the output rows; a violated premise or a redundant
+        // sink falls through to the exact unfused path below
+        using SE = SplitEmitTraits<L2>;
+        const uint64_t nout = M + 1;
+        uint8_t *W = (uint8_t *)c.ws.get(Workspace::OW, nout);
+        uint8_t *last = (uint8_t *)c.ws.get(Workspace::OLAST, nout);
+        uint32_t *weights = COUNTED ? (uint32_t *)c.ws.get(Workspace::OWEIGHTS, nout * 4) : nullptr;
+        uint64_t *pos = (uint64_t *)c.ws.get(Workspace::DPOS, D * 8);
+        uint8_t *wl = (uint8_t *)c.ws.get(Workspace::DWL, D);
+        const uint64_t ntiles = ceil_div(nout, SE::TILE);
+        uint64_t *jsplit = (uint64_t *)c.ws.get(Workspace::SPLITS, (ntiles + 1) * 8);
+        reset_small(c);
+        if (D) {
+            const bool idx = bidx_valid(c, real, R);
+            dummy_rank_kernel<L2, L3><<<dim3((unsigned)ceil_div(D, 256)), dim3(256), 0, c.stream>>>(
+                real, R, dk, D, K, idx ? c.build.bidx : nullptr, c.build.bidx_shift, root ? 2 : 1, pos, wl,
+                &c.small->skip, &c.small->root_same);
+            HIP_CHECK(hipGetLastError());
+        }
+        split_points_kernel<SE::TILE><<<dim3((unsigned)ceil_div(ntiles + 1, 256)), dim3(256), 0, c.stream>>>(
+            pos, D, ntiles, jsplit);
+        HIP_CHECK(hipGetLastError());
+        split_emit_kernel<L2, COUNTED><<<dim3((unsigned)ntiles), dim3(SE::BLOCK), 0, c.stream>>>(
+            real, realc, R, pos, wl, jsplit, nout, root ? 1 : 0, &c.small->root_same, wmax, W, last, weights);
+        HIP_CHECK(hipGetLastError());
+        f_bounds_split_kernel<L3, L2><<<1, 64, 0, c.stream>>>(real, R, dk, D, K, root ? 1 : 0, c.small->fhist);
+        HIP_CHECK(hipGetLastError());
+        *ev_merge = tm.mark();
+        Small h;
+        HIP_CHECK(hipMemcpyAsync(&h, c.small, sizeof(Small), hipMemcpyDeviceToHost, c.stream));
+        HIP_CHECK(hipStreamSynchronize(c.stream));
+        if (!h.skip) {
+            for (int ch = 0; ch < 5; ++ch) out->F[ch] = h.fhist[ch];
+            out->W = W;
+            out->last = last;
+            out->weights = weights;
+            out->n = nout;
+            out->n_real = R;
+            out->n_dummy = M - R;
+            return;
+        }
+    }
+    K3 *sk = (K3 *)c.ws.get(Workspace::STREAM, M * sizeof(K3));
+    uint32_t *sc = COUNTED ? (uint32_t *)c.ws.get(Workspace::SCOUNT, M * 4) : nullptr;
+    if (root) {
+        set_root_row_kernel<<<1, 1, 0, c.stream>>>((uint64_t *)sk, L3, COUNTED ? sc : nullptr);
+        HIP_CHECK(hipGetLastError());
+    }
+    merge_sorted<L3, L2, true, COUNTED, false>(c, real, realc, R, dk, nullptr, D, K, sk, sc, root ? 1 : 0);
+    debug_check_sorted(c, "merged stream", sk, M);
+    *ev_merge = tm.mark();
+    emit_stream<L3, COUNTED>(c, k, wmax, sk, sc, M, R, out);
+}
+
 template <int L2, bool COUNTED>
 static bool want_spill(Ctx &c, unsigned K, bool canonical, const BuildInput &in, uint32_t P);
 template <int L2, int L3, bool COUNTED>
@@ -3180,8 +1438,6 @@ static void run_pipeline(Ctx &c, unsigned k, bool canonical, unsigned bits,
     const uint32_t cmax = cbits == 8 ? 0xFFu : cbits == 16 ? 0xFFFFu : 0xFFFFFFFFu;
     mtg_boss_timings &T = c.timings;
     T = mtg_boss_timings{};
-    note_bucket_index(c, nullptr, 0, nullptr, 0);
-    c.gap = Ctx::GappedSet{};
     T.world = 1;
     T.n_batches = 1;
     HIP_CHECK(hipMemsetAsync(c.small, 0, sizeof(Small), c.stream));
@@ -3194,11 +1450,8 @@ static void run_pipeline(Ctx &c, unsigned k, bool canonical, unsigned bits,
     uint32_t *ca, *cb;
     uint64_t N = 0;
     double dup = 0;
-    const uint32_t *hist1 = nullptr;
+    SortRequest<L2> rq;  // the collect sort's (stage_extract_fused tells it the level it already ran)
     MsdPlan fplan{};
-    c.radix_ms = 0;
-    c.radix_bytes = 0;
-    c.radix_launches = 0;
     const uint32_t P = plan_ranges<L2, COUNTED>(c, K, canonical, in);
     if (want_spill<L2, COUNTED>(c, K, canonical, in, P)) {  // not even the real edges fit: spill
         run_pipeline_spill<L2, L3, COUNTED>(c, k, canonical, bits, in, P, out);
@@ -3227,20 +1480,20 @@ static void run_pipeline(Ctx &c, unsigned k, bool canonical, unsigned bits,
     } else {
     if (stage_extract_windows<L2, COUNTED>(c, K, canonical, cmax, in, &ka, &kb, &ca, &cb, &N))
         dup = 1.0;  // one k-mer per record: distinct up to a strand
-    else if (!stage_extract_fused<L2, COUNTED>(c, K, canonical, cmax, in, &ka, &kb, &ca, &cb, &N, &dup, &hist1,
-                                                &fplan))
+    else if (!stage_extract_fused<L2, COUNTED>(c, K, canonical, cmax, in, &ka, &kb, &ca, &cb, &N, &dup, &rq, &fplan))
         N = stage_extract<L2, COUNTED>(c, K, canonical, cmax, in, &ka, &kb, &ca, &cb);
     ev_extract = tm.mark();
 
     // ---- K2 sort + K3 unique / saturating count merge (ka)
-    c.want_gidx = canonical;  // the fused rc merge reads the canonical keys' bucket index
-    c.defer_gather_req = canonical;  // ... and may read them in their speculative buckets (Ctx::gap)
-    U = stage_collect<L2, COUNTED>(c, K, cmax, &ka, &kb, &ca, &cb, N, dup, true, hist1, &fplan);
-    c.defer_gather_req = false;
-    c.want_gidx = false;
+    rq.track_partition = true;
+    rq.want_gidx = canonical;  // the fused rc merge reads the canonical keys' bucket index
+    rq.defer_gather = canonical;  // ... and may read them in their speculative buckets (BuildState::gap)
+    U = stage_collect<L2, COUNTED>(c, K, cmax, &ka, &kb, &ca, &cb, N, dup, rq);
+    c.build.gidx = rq.gidx;
+    c.build.gap = rq.gap;
     ev_sort = tm.mark();
     T.n_unique = U;
-    if (c.debug) ensure_compact(c);
+    if (c.knobs.debug) ensure_compact(c);
     debug_check_sorted(c, "collected k-mers", ka, U);
     ev_unique = tm.mark();
 
@@ -3255,6 +1508,7 @@ static void run_pipeline(Ctx &c, unsigned k, bool canonical, unsigned bits,
         K2 *real = (K2 *)c.ws.get(Workspace::REAL, 2 * U * sizeof(K2));
         uint32_t *realc = COUNTED ? (uint32_t *)c.ws.get(Workspace::REALC, 2 * U * 4) : nullptr;
         RcMerge<L2> rm{ka, ca, U, real, realc};
+        rm.cidx = std::exchange(c.build.gidx, GroupIndex{});
         // the dummy stage's bucket index (stage_dummies_local) comes out of the fused merge, sized
         // for R = 2U (odd K; even K loses its palindromes, and the dummy stage rebuilds the index
         // when that changes its size)
@@ -3278,7 +1532,6 @@ static void run_pipeline(Ctx &c, unsigned k, bool canonical, unsigned bits,
                             Workspace::RC_ALTC, Workspace::SPEC_A, Workspace::SPEC_B, Workspace::SPEC_AC,
                             Workspace::SPEC_BC})
                 c.ws.release(sl);
-            c.gidx = Ctx::GroupIndex{};  // it indexed the CANON block given back above
         }
     }
     ensure_compact(c);  // (a no-op unless the canonical set is still in buckets)
@@ -3312,9 +1565,9 @@ static void run_pipeline(Ctx &c, unsigned k, bool canonical, unsigned bits,
     T.merge_ms = tm.ms(ev_dummy, ev_merge);
     T.emit_ms = tm.ms(ev_merge, ev_emit);
     T.total_ms = tm.ms(ev_start, ev_emit);
-    T.radix_launches = c.radix_launches;
-    T.radix_pass_ms = c.radix_launches ? c.radix_ms / c.radix_launches : 0;
-    T.radix_bytes = c.radix_launches ? c.radix_bytes / c.radix_launches : 0;
+    T.radix_launches = c.build.radix_launches;
+    T.radix_pass_ms = c.build.radix_launches ? c.build.radix_ms / c.build.radix_launches : 0;
+    T.radix_bytes = c.build.radix_launches ? c.build.radix_bytes / c.build.radix_launches : 0;
     T.peak_bytes = c.ws.held();
 }
 
@@ -3426,7 +1679,7 @@ static uint32_t dist_coresident(Ctx &c, Dist &d) {
 // a rank's HBM budget for planning its rounds: memory_preallocated, else its share of the free HBM
 // (the ranks on its GPU split it) plus what its workspace holds
 static double dist_budget(const Ctx &c, const Dist &d) {
-    if (c.mem_budget > 0) return c.mem_budget;
+    if (c.params.mem_budget > 0) return c.params.mem_budget;
     size_t fr = 0, tot = 0;
     HIP_CHECK(hipMemGetInfo(&fr, &tot));
     return 0.9 * ((double)fr / (double)std::max<uint32_t>(d.coresident, 1) + (double)c.ws.held());
@@ -3585,13 +1838,13 @@ static uint32_t plan_rounds_dist(Ctx &c, Dist &d, unsigned K, bool canonical, co
     const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
     // bins of RB_CHARS node chars keep every emission group on one rank only for k - 1 >= RB_CHARS
     const bool can = K >= RB_CHARS + 2;
-    if (can && c.force_ranges) {
-        want = c.force_ranges;
+    if (can && c.knobs.force_ranges) {
+        want = c.knobs.force_ranges;
     } else if (can) {
         const double per_key = (double)sizeof(Key<L2>) + (COUNTED ? 4.0 : 0.0);
         const double budget = dist_budget(c, d);
         // single pass: KA + KB over every window, the exchange buffers and the owned real edges
-        if ((double)npos * per_key * 3.0 > budget || c.disk) {
+        if ((double)npos * per_key * 3.0 > budget || c.params.disk) {
             const double keys = (double)npos * (canonical ? 2.0 : 1.0);
             // a round holds its extracted keys twice (sort ping-pong), the received runs twice
             want = (uint64_t)std::ceil(keys * per_key * 4.0 / (0.4 * budget));
@@ -3686,9 +1939,9 @@ static uint64_t collect_ranges_dist(Ctx &c, Dist &d, unsigned K, bool canonical,
             if (N != nj) throw std::runtime_error("range extraction count differs from its histogram");
             const double spread = (double)RB_BINS / (double)std::max<uint32_t>(1, sel.size());
             const double dup = estimate_dup<L2>(c, ka, N, 8.0) / spread;
-            c.track_partition = r == 0;  // the roofline's partition pass: the first round's first level
-            Ul = msd_sort_unique<L2, COUNTED>(c, &ka, &kb, &ca, &cb, N, 2 * K, cmax, dup);
-            c.track_partition = false;
+            SortRequest<L2> rq;
+            rq.track_partition = r == 0;  // the roofline's partition pass: the first round's first level
+            Ul = msd_sort_unique<L2, COUNTED>(c, &ka, &kb, &ca, &cb, N, 2 * K, cmax, dup, rq);
         }
         extracted += nj;
         tr("round collect", nj, Ul);
@@ -3717,8 +1970,9 @@ static uint64_t collect_ranges_dist(Ctx &c, Dist &d, unsigned K, bool canonical,
                 // the keys fill this owner's batch of the bins: plan as if spread over all of them
                 const double spread = (double)RB_BINS / (double)std::max<uint64_t>(1, bb[d.me][r + 1] - bb[d.me][r]);
                 const double dup1 = estimate_dup<L2>(c, xa, n1, 1.0) / spread;
-                U = msd_sort_unique<L2, COUNTED>(c, &xa, &xb, &xac, &xbc, n1, 2 * K, cmax, dup1, nullptr, false,
-                                                 &runs);
+                SortRequest<L2> rq;
+                rq.runs = &runs;
+                U = msd_sort_unique<L2, COUNTED>(c, &xa, &xb, &xac, &xbc, n1, 2 * K, cmax, dup1, rq);
             }
             tr("round exchange + merge", n1, U);
         }
@@ -3761,7 +2015,7 @@ static uint64_t collect_ranges_dist(Ctx &c, Dist &d, unsigned K, bool canonical,
 // the local-collect path).
 // the routed collect needs the fused K1 (u64 keys); MTG_COLLECT=ranges keeps the key-range collect
 static bool routed_applies(const Ctx &c, unsigned K) {
-    return c.fused && !c.use_lsd && K - 1 >= FUSED_HB / 2 && K <= 32 && !c.range_scan;
+    return c.knobs.fused && !c.knobs.use_lsd && K - 1 >= FUSED_HB / 2 && K <= 32 && !c.knobs.range_scan;
 }
 
 // one-window reads (KMC input) on every rank: cheaper through window_reads_kernel and the local
@@ -3896,16 +2150,16 @@ static uint64_t routed_pieces(Ctx &c, Dist &d, unsigned K, uint32_t cmax, const 
             fp.levels = 1 + (T - B1 + MSD_DBITS - 1) / MSD_DBITS;
             fp.digit_end[1] = B1;
             for (unsigned l = 2; l <= fp.levels; ++l) fp.digit_end[l] = B1 + (T - B1) * (l - 1) / (fp.levels - 1);
-            c.track_partition = q == 0;
+            SortRequest<1> rq;
+            rq.hist1 = dh1;
+            rq.level1_done = true;
+            rq.force_plan = &fp;
+            rq.track_partition = q == 0;
             // the sort's final gather writes the piece's distinct keys straight after the previous pieces' (no
             // append copy: 0.9 ms a rank-step at P = 2 with 4 pieces); CANON is neither its input nor its tmp
-            c.sort_out = acc + off;
-            c.sort_out_vals = COUNTED ? accc + off : nullptr;
-            Ur = msd_sort_unique<1, COUNTED>(c, &pa, &pb, &pac, &pbc, nq, 2 * K, cmax, dup, dh1, false, nullptr, true,
-                                             nullptr, &fp);
-            c.sort_out = nullptr;
-            c.sort_out_vals = nullptr;
-            c.track_partition = false;
+            rq.out = acc + off;
+            rq.out_vals = COUNTED ? accc + off : nullptr;
+            Ur = msd_sort_unique<1, COUNTED>(c, &pa, &pb, &pac, &pbc, nq, 2 * K, cmax, dup, rq);
             if (Ur && pa != acc + off) {  // (a path without the final gather)
                 HIP_CHECK(hipMemcpyAsync(acc + off, pa, Ur * sizeof(K2), hipMemcpyDeviceToDevice, c.stream));
                 if (COUNTED) HIP_CHECK(hipMemcpyAsync(accc + off, pac, Ur * 4, hipMemcpyDeviceToDevice, c.stream));
@@ -4065,11 +2319,11 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
     constexpr unsigned OB = 8;   // owner-range prefix bits (4 node chars: whole chars for the lifted bounds)
     // canonical windows keep the strand whose key top hashes smaller (boss_kernels.hpp: take_rc): the
     // owners' canonical keys then follow the real edges, and one set of ranges balances both
-    const int cmode = canonical ? (c.routed_min || d.P == 1 ? 1 : 2) : 0;
+    const int cmode = canonical ? (c.knobs.routed_min || d.P == 1 ? 1 : 2) : 0;
     // pass B's scatter digit: 10 bits across ranks (extract_partition_fast_kernel<512, 1024>), so that an
     // owner of 2 ranks' worth of keys at configs[1]'s density (19 planned bits) keeps a 2-level sort;
     // the counted pass B takes 9
-    const unsigned B1 = c.fused_b1 ? std::max(c.fused_b1, OB) : (!COUNTED && c.wide_b1 && d.P >= 2) ? 10u : 9u;
+    const unsigned B1 = c.knobs.fused_b1 ? std::max(c.knobs.fused_b1, OB) : (!COUNTED && c.knobs.wide_b1 && d.P >= 2) ? 10u : 9u;
     const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
     c.timings.n_positions = npos;
     constexpr int TILE = ExtractTraits<1>::TILE;
@@ -4077,7 +2331,7 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
     const int fbk = 512;
     const uint32_t rps = (uint32_t)(16 * fbk / TILE);
     // (stripe_cursor_kernel takes at most 1024 stripes: 2048 rows at rps = 2, 1024 at rps = 1)
-    uint32_t nrows = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(tiles, c.hist_rows), 1024ull * rps);
+    uint32_t nrows = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(tiles, c.knobs.hist_rows), 1024ull * rps);
     if (nrows >= rps) nrows -= nrows % rps;
     constexpr uint32_t NBH = 1u << FUSED_HB;
     // pass A: per-row histograms of the canonical keys' top 12 bits (and of the other strand's)
@@ -4152,7 +2406,7 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
     uint32_t rounds = 1;
     bool pipe_ok = false;  // the rounds' exchanges pipelined (routed_rounds_pipelined)
     {
-        uint64_t want = c.force_ranges;
+        uint64_t want = c.knobs.force_ranges;
         const double budget = dist_budget(c, d);
         const double per_key = 8.0 + (COUNTED ? 4.0 : 0.0);
         if (!want) {
@@ -4173,8 +2427,8 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
         uint64_t r = 1, nmax = 0;
         for (int i = 0; i < d.P; ++i) r = std::max(r, all[3 * i]), nmax = std::max(nmax, all[3 * i + 1]);
         rounds = (uint32_t)std::min<uint64_t>(r, 64);
-        pipe_ok = c.dist_pieces > 1;
-        for (int i = 0; i < d.P && pipe_ok && !c.force_ranges; ++i)
+        pipe_ok = c.knobs.dist_pieces > 1;
+        for (int i = 0; i < d.P && pipe_ok && !c.knobs.force_ranges; ++i)
             pipe_ok = 5.0 * (double)nmax / rounds * per_key <= 0.6 * (double)all[3 * i + 2];
     }
     // global level-1 counts, and every owner's bucket interval cut into the rounds
@@ -4284,12 +2538,14 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
         fp.levels = 1 + (T - B1 + MSD_DBITS - 1) / MSD_DBITS;
         fp.digit_end[1] = B1;
         for (unsigned l = 2; l <= fp.levels; ++l) fp.digit_end[l] = B1 + (T - B1) * (l - 1) / (fp.levels - 1);
-        c.track_partition = track;
-        c.want_gidx = gidx;
-        const uint64_t u = msd_sort_unique<1, COUNTED>(c, pa, pb, pac, pbc, n1, 2 * K, cmax, dup, dh1, false, nullptr,
-                                                       true, nullptr, &fp);
-        c.want_gidx = false;
-        c.track_partition = false;
+        SortRequest<1> rq;
+        rq.hist1 = dh1;
+        rq.level1_done = true;
+        rq.force_plan = &fp;
+        rq.track_partition = track;
+        rq.want_gidx = gidx;
+        const uint64_t u = msd_sort_unique<1, COUNTED>(c, pa, pb, pac, pbc, n1, 2 * K, cmax, dup, rq);
+        if (gidx) c.build.gidx = rq.gidx;
         return u;
     };
     // the rounds' distinct keys appended to the owned canonical set (sized from the first filled round's
@@ -4332,8 +2588,8 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
         // exchange 1 in pieces under the owner sort (routed_pieces): pieces of at least 2^28 keys an owner
         // (each piece's sort pays ~0.7 ms of its own launches and host reads, more than a smaller piece's
         // sort can hide), exactly MTG_DIST_PIECES when given; the same count on every rank (global totals)
-        const uint32_t Q = c.dist_pieces_set ? c.dist_pieces
-                                             : (uint32_t)std::min<uint64_t>(c.dist_pieces,
+        const uint32_t Q = c.knobs.dist_pieces_set ? c.knobs.dist_pieces
+                                             : (uint32_t)std::min<uint64_t>(c.knobs.dist_pieces,
                                                                             std::max<uint64_t>(1, Nall / d.P >> 28));
         if (rounds == 1 && d.P > 1 && Q > 1) {
             double span = 0, hidden = 0;
@@ -4413,7 +2669,7 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
 // other owner's.  Returns false where the path does not apply (the caller collects its own reads).
 static bool dist_superkmers(Ctx &c, Dist &d, unsigned K, bool canonical, const BuildInput &in, BuildInput *out,
                             Tracer &tr) {
-    if (c.dist_collect != 0 || d.P < 2 || d.P > SK_MAX_OWNERS || K < 20 || K + 16 > (unsigned)SK_KMAX) return false;
+    if (c.knobs.dist_collect != 0 || d.P < 2 || d.P > SK_MAX_OWNERS || K < 20 || K + 16 > (unsigned)SK_KMAX) return false;
     const unsigned M = std::min(11u, K - 12);
     const uint32_t P = (uint32_t)d.P;
     const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
@@ -4524,7 +2780,6 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
     const uint32_t cmax = cbits == 8 ? 0xFFu : cbits == 16 ? 0xFFFFu : 0xFFFFFFFFu;
     mtg_boss_timings &T = c.timings;
     T = mtg_boss_timings{};
-    note_bucket_index(c, nullptr, 0, nullptr, 0);
     HIP_CHECK(hipMemsetAsync(c.small, 0, sizeof(Small), c.stream));
     EventTimer tm(c.stream);
     const int ev_start = tm.mark();
@@ -4541,9 +2796,6 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
     d.nb = 1ull << (2 * d.m);
 
     Tracer tr{c, d.me};
-    c.radix_ms = 0;
-    c.radix_bytes = 0;
-    c.radix_launches = 0;
     int ev_extract, ev_sort, ev_unique;
     K2 *E = nullptr;
     uint32_t *Ec = nullptr;
@@ -4551,7 +2803,7 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
     std::vector<uint64_t> bounds;
     // the routed collect plans its own rounds (canonical k-mers of the fused K1); the other collects
     // batch in key ranges that re-scan the reads
-    bool routed_try = L2 == 1 && c.dist_collect != 2 && !c.disk && routed_applies(c, K);
+    bool routed_try = L2 == 1 && c.knobs.dist_collect != 2 && !c.params.disk && routed_applies(c, K);
     if (routed_try) routed_try = !dist_window_input(c, d, K, in);
     const uint32_t rounds = routed_try ? 1 : plan_rounds_dist<L2, COUNTED>(c, d, K, canonical, in);
     if (rounds > 1) {
@@ -4584,7 +2836,7 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
         uint32_t *ca, *cb;
         uint64_t N = 0;
         double dup = 0;
-        const uint32_t *hist1 = nullptr;
+        SortRequest<L2> rq;
         MsdPlan fplan{};
         // a super-k-mer owner keeps the representative whose top bits hash smaller (cmode 2): its keys
         // spread evenly over the key space instead of piling up at small prefixes (min(fwd, rc)), so the
@@ -4597,7 +2849,7 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
         if (sk && d.P > 1) c.canon_mode = 2;
         if (stage_extract_windows<L2, COUNTED>(c, K, canonical, cmax, cin, &ka, &kb, &ca, &cb, &N))
             dup = 1.0;
-        else if (!stage_extract_fused<L2, COUNTED>(c, K, canonical, cmax, cin, &ka, &kb, &ca, &cb, &N, &dup, &hist1,
+        else if (!stage_extract_fused<L2, COUNTED>(c, K, canonical, cmax, cin, &ka, &kb, &ca, &cb, &N, &dup, &rq,
                                                     &fplan))
             N = stage_extract<L2, COUNTED>(c, K, canonical, cmax, cin, &ka, &kb, &ca, &cb);
         c.canon_mode = mode_scope.old;
@@ -4606,7 +2858,8 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
         }
         ev_extract = tm.mark();
         tr("extract", N);
-        const uint64_t Ul = stage_collect<L2, COUNTED>(c, K, cmax, &ka, &kb, &ca, &cb, N, dup, true, hist1, &fplan);
+        rq.track_partition = true;
+        const uint64_t Ul = stage_collect<L2, COUNTED>(c, K, cmax, &ka, &kb, &ca, &cb, N, dup, rq);
         ev_sort = tm.mark();
         tr("local collect", Ul);
 
@@ -4636,10 +2889,11 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
                 // their counts add with saturation (sorted_multiset.cpp:54-84).  The keys cover ~1/P of
                 // the prefix space: P times denser buckets than their count says
                 const double dup1 = estimate_dup<L2>(c, xa, n1, 1.0) / d.P;
-                c.want_gidx = canonical;
-                T.n_unique = msd_sort_unique<L2, COUNTED>(c, &xa, &xb, &xac, &xbc, n1, 2 * K, cmax, dup1, nullptr,
-                                                          false, &runs);
-                c.want_gidx = false;
+                SortRequest<L2> urq;
+                urq.runs = &runs;
+                urq.want_gidx = canonical;
+                T.n_unique = msd_sort_unique<L2, COUNTED>(c, &xa, &xb, &xac, &xbc, n1, 2 * K, cmax, dup1, urq);
+                c.build.gidx = urq.gidx;
             }
         }
         }
@@ -4698,18 +2952,22 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
                 const MsdPlan rp = msd_plan<L2>(c, nrc, 2 * K, dupm);
                 const unsigned fb = rp.levels ? rp.digit_end[rp.levels] : 0;
                 if (fb && fb <= 26 &&
-                    !(c.gidx.keys == (const void *)xa && c.gidx.n == U && c.gidx.bits == fb && c.gidx.nbits == 2 * K)) {
+                    !(c.build.gidx.keys == (const void *)xa && c.build.gidx.n == U && c.build.gidx.bits == fb && c.build.gidx.nbits == 2 * K)) {
                     const uint64_t nbk = 1ull << fb;
                     uint64_t *gi = (uint64_t *)c.ws.get(Workspace::CANON_IDX, (nbk + 2) * 8);
                     bucket_index<L2>(c, xa, U, 2 * K - fb, nbk, gi);
                     HIP_CHECK(hipMemcpyAsync(gi + nbk + 1, gi + nbk, 8, hipMemcpyDeviceToDevice, c.stream));
-                    c.gidx = Ctx::GroupIndex{xa, U, fb, 2 * K, gi};
+                    c.build.gidx = GroupIndex{xa, U, fb, 2 * K, gi};
                 }
             }
             uint64_t nr = 0;
-            if (nrc)
-                nr = msd_sort_unique<L2, COUNTED>(c, &rkeys, &ralt, &rcc, &rcalt, nrc, 2 * K, cmax, dupm, nullptr, true,
-                                                  nullptr, false, U ? &rm : nullptr);
+            if (nrc) {
+                SortRequest<L2> rrq;
+                rrq.distinct = true;
+                rrq.rm = U ? &rm : nullptr;
+                rm.cidx = std::exchange(c.build.gidx, GroupIndex{});
+                nr = msd_sort_unique<L2, COUNTED>(c, &rkeys, &ralt, &rcc, &rcalt, nrc, 2 * K, cmax, dupm, rrq);
+            }
             if (!rm.done) merge_sorted<L2, L2, false, COUNTED, true>(c, xa, xac, U, rkeys, rcc, nr, K, out, outc, 0);
             R = U + nr;
             E = out;
@@ -4728,7 +2986,7 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
     if (d.P == 1) {  // one rank owns every target node: the single build's local join
         D = stage_dummies_local<L2, L3>(c, K, E, R, &dk);
         tr("dummies (local)", D);
-    } else if (c.dist_pull && d.m + 1 <= k_b) {
+    } else if (c.knobs.dist_pull && d.m + 1 <= k_b) {
         // the pulled sink join (dist_kernels.hpp: pull_bounds_kernel): every rank sends each owner the
         // slices of its edges whose nodes the owner's edges target, the owner runs the single build's
         // join (dummy_sink_kernel) of its edges against them and returns an in-edge byte per received
@@ -4998,9 +3256,9 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
     T.total_ms = tm.ms(ev_start, ev_emit);
     for (auto &p : d.xev) T.exchange_ms += tm.ms(p.first, p.second);
     T.sent_bytes = comm.sent_bytes - sent0;
-    T.radix_launches = c.radix_launches;
-    T.radix_pass_ms = c.radix_launches ? c.radix_ms / c.radix_launches : 0;
-    T.radix_bytes = c.radix_launches ? c.radix_bytes / c.radix_launches : 0;
+    T.radix_launches = c.build.radix_launches;
+    T.radix_pass_ms = c.build.radix_launches ? c.build.radix_ms / c.build.radix_launches : 0;
+    T.radix_bytes = c.build.radix_launches ? c.build.radix_bytes / c.build.radix_launches : 0;
     T.peak_bytes = c.ws.held();
 }
 
@@ -5107,10 +3365,10 @@ class NoComm : public Comm {
 template <int L2, bool COUNTED>
 static bool want_spill(Ctx &c, unsigned K, bool canonical, const BuildInput &in, uint32_t P) {
     if (P < 2 || !c.host_output || K < RB_CHARS + 2) return false;
-    if (c.force_spill) return true;
-    if (!c.disk) return false;
+    if (c.knobs.force_spill) return true;
+    if (!c.params.disk) return false;
     const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
-    double budget = c.mem_budget;
+    double budget = c.params.mem_budget;
     if (budget <= 0) {
         size_t fr = 0, tot = 0;
         HIP_CHECK(hipMemGetInfo(&fr, &tot));
@@ -5157,7 +3415,7 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
     const std::vector<uint64_t> bounds = balanced_bounds(hist.data(), RB_BINS, (int)P);
     NoComm nocomm((int)P);
     Dist d{nocomm, (int)P, 0, RB_CHARS, 2 * K - 2 * RB_CHARS, RB_BINS, &tm, {}};
-    SpillStore st(c.disk ? c.swap_dir : std::string(), c.disk_cap);
+    SpillStore st(c.params.disk ? c.params.swap_dir : std::string(), c.params.disk_cap);
     uint32_t *tcnt = (uint32_t *)c.ws.get(Workspace::DTCNT, (tiles + 1) * 4);
     uint64_t *toff = (uint64_t *)c.ws.get(Workspace::DTOFF, (tiles + 1) * 8);
     std::vector<uint32_t> eid(P), ecid(P), qid(P);
@@ -5194,7 +3452,8 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
                 throw std::runtime_error("range extraction count differs from its histogram");
             const double spread = (double)RB_BINS / (double)(hi - lo);
             const double dup = estimate_dup<L2>(c, ka, nj, 8.0) / spread;
-            U = msd_sort_unique<L2, COUNTED>(c, &ka, &kb, &ca, &cb, nj, 2 * K, cmax, dup);
+            SortRequest<L2> rq;
+            U = msd_sort_unique<L2, COUNTED>(c, &ka, &kb, &ca, &cb, nj, 2 * K, cmax, dup, rq);
         }
         rn[j] = U;
         eid[j] = st.put(ka, U * sizeof(K2), c.stream);
@@ -5544,7 +3803,8 @@ static uint64_t kmc_count_write(Ctx &c, const BuildInput &in, unsigned K, bool c
             (uint64_t *)ka, N, K, canonical ? 1 : 0);
         HIP_CHECK(hipGetLastError());
         const double dup = estimate_dup<1>(c, ka, N, 8.0);
-        U = msd_sort_unique<1, true>(c, &ka, &kb, &ca, &cb, N, 2 * K, 0xFFFFFFFFu, dup);
+        SortRequest<1> rq;
+        U = msd_sort_unique<1, true>(c, &ka, &kb, &ca, &cb, N, 2 * K, 0xFFFFFFFFu, dup, rq);
     }
     check_error_word(c);
     std::vector<uint64_t> keys(U);
@@ -5698,12 +3958,11 @@ mtg_boss_ctor *mtg_boss_ctor_create(const mtg_boss_params *p) {
         HIP_CHECK(hipSetDevice(c->device));
         HIP_CHECK(hipStreamCreateWithFlags(&c->ctx.stream, hipStreamNonBlocking));
         HIP_CHECK(hipMalloc(&c->ctx.small, sizeof(Small)));
-        load_knobs(c->ctx);
-        c->ctx.mem_budget = p->memory_preallocated;
-        c->ctx.swap_dir = p->swap_dir ? p->swap_dir : "";
-        c->ctx.disk_cap = p->disk_cap_bytes;
+        c->ctx.params.mem_budget = p->memory_preallocated;
+        c->ctx.params.swap_dir = p->swap_dir ? p->swap_dir : "";
+        c->ctx.params.disk_cap = p->disk_cap_bytes;
         // the disk container bounds memory: always collect in key ranges (boss_chunk_construct.cpp:664-933)
-        if (p->container_type == MTG_CONTAINER_VECTOR_DISK && !c->ctx.force_ranges) c->ctx.disk = true;
+        if (p->container_type == MTG_CONTAINER_VECTOR_DISK && !c->ctx.knobs.force_ranges) c->ctx.params.disk = true;
     } catch (const std::exception &e) {
         set_error(e.what());
         delete c;
@@ -5738,9 +3997,6 @@ int mtg_boss_ctor_trim(mtg_boss_ctor *c) {
         // the last build's stage buffers too (its device chunk arrays stay valid): a configs[2] build
         // holds ~200 GB in them, and a second constructor in the same process had 110 MiB left
         c->ctx.ws.release_stage_buffers(true);
-        note_bucket_index(c->ctx, nullptr, 0, nullptr, 0);
-        c->ctx.gap.valid = false;
-        c->ctx.gidx = Ctx::GroupIndex{};
         c->ctx.ws.drop_cache();
         c->ctx.timings.cached_bytes = 0;
         return MTG_OK;
@@ -5820,8 +4076,8 @@ int mtg_boss_ctor_add_kmc(mtg_boss_ctor *c, const char *kmc_path, uint64_t min_c
         // the first database of a batch is copied to the device while its files are read (the
         // workspace's KMC slots; a later database is copied by build_chunk, the slots being taken)
         std::unique_lock<std::mutex> lock(c->kmc_mu, std::defer_lock);
-        if (c->ctx.kmc_mirror) lock.lock();
-        const bool mirror = c->ctx.kmc_mirror && c->kmc.empty();
+        if (c->ctx.knobs.kmc_mirror) lock.lock();
+        const bool mirror = c->ctx.knobs.kmc_mirror && c->kmc.empty();
         DeviceGuard g(c->device);
         DeviceMirror mpre, msuf;
         mpre.stream = msuf.stream = c->ctx.stream;
@@ -5937,6 +4193,7 @@ static const char *kSuffixDist =
 
 // the build on the device buffers: the suffix route or the full construction
 static void dispatch_build(mtg_boss_ctor *c, mtg::Comm *comm, const BuildInput &in_, BuildOutput *out) {
+    mtg::reset_build_state(c->ctx);  // nothing of the previous build (a failed one included) is carried over
     BuildInput in = in_;
     if (in.read_counts && in.n_reads > 1) {  // bracket the per-read count searches (device_common.hpp)
         const uint64_t nq = (in.seq_len >> mtg::RID_SHIFT) + 2;
@@ -6066,8 +4323,6 @@ static void unpack_w4(const uint8_t *in, uint64_t nbytes, uint8_t *out) {
         out[2 * i + 1] = in[i] >> 4;
     }
 }
-
-static unsigned stage_threads(const mtg_boss_ctor *c);
 
 // W[0..n) on the device -> host W (out, n bytes): 4-bit pieces of 16 MiB, unpacked as they land
 static void copy_w_to_host(mtg_boss_ctor *c, const uint8_t *dW, uint64_t n, uint8_t *out) {
@@ -6935,7 +5190,7 @@ uint64_t write_dbg_device_impl(Ctx &ctx, const mtg_boss_device_chunk &ch, unsign
     }
     double stage_ms[5] = {0, 0, 0, 0, 0};
     const uint64_t n_valid = dbgio::write_dbg_payload(base, P, ch.F, k, mode, stage_ms);
-    if (ctx.trace)
+    if (ctx.knobs.trace)
         fprintf(stderr, "[mtg trace] write_dbg_device host: wt_huff %.1f ms, last %.1f ms, index+framing %.1f ms, "
                         "edgemask %.1f ms, weights %.1f ms\n",
                 stage_ms[0], stage_ms[1], stage_ms[2], stage_ms[3], stage_ms[4]);

@@ -119,6 +119,26 @@ def test_rounds_memory_budget_plans(small_fused, transcripts_1000):
     assert t2.n_batches == 1 and t2.collect_mode == 0 and np.array_equal(got.W, got2.W)
 
 
+def test_builds_in_sequence_share_nothing(small_fused, transcripts_1000):
+    # one constructor, three builds: rounds (each round's sort is told its output destination, its share
+    # of the set's index and the spare buffers), then a one-pass build (deferred gather, group index),
+    # then the rounds again -- nothing one build told its sorts or kept for its rc stage reaches the next
+    small = _random_reads(77, 20, 150, 5000)
+    want_big = O.build_chunk(30, transcripts_1000, canonical=True)
+    want_small = O.build_chunk(30, small, canonical=True)
+    ctor = boss.IBOSSChunkConstructor.initialize(30, both_strands=True, memory_preallocated=16e6)
+    for step, (seqs, want) in enumerate(((transcripts_1000, want_big), (small, want_small),
+                                         (transcripts_1000, want_big))):
+        ctor.add_sequences(seqs)
+        got = ctor.build_chunk()
+        t = ctor.timings()
+        assert_same(got, want, "build %d of 3 on one constructor" % (step + 1))
+        if step == 1:
+            assert t.n_batches == 1, t.n_batches
+        else:
+            assert t.collect_mode == ROUNDS, (t.collect_mode, t.n_batches)
+
+
 def test_range_scan_knob(small_fused, transcripts_1000):
     # MTG_COLLECT=ranges keeps the key-range collect (both strands, re-scanned reads) for the same input
     small_fused.setenv("MTG_RANGES", "3")
@@ -148,7 +168,7 @@ def test_rounds_bench_generator_2m(monkeypatch, canonical, bits):
 
 
 # a 3-level plan in every round (configs[3]'s share plans 10 + 16 + 22 bits): forced on 2 M reads.  The
-# speculative level 3 partitions into the rounds' level-1 array (c.spec_into) and its local unique writes
+# speculative level 3 partitions into the rounds' level-1 array (SortRequest::spec_into) and its local unique writes
 # over its own buckets; MTG_SPEC_INPLACE=0 gives it two buffers of its own, MTG_WS_CARVE=1 makes every
 # workspace request a piece carved off a kept block where one holds it (the allocator's no-room path)
 @pytest.mark.parametrize("spec3,knobs", [("0", {}), ("1", {}), ("1", {"MTG_WS_CARVE": "1"}),

@@ -71,8 +71,9 @@ static int check(Ctx &c, uint64_t n, unsigned nbits, int dupf, uint32_t seed, bo
     HIP_CHECK(hipMemcpy(va, hv.data(), n * 4, hipMemcpyHostToDevice));
     Key<L> *ka = a, *kb = b;
     uint32_t *pa = va, *pb = vb;
-    uint64_t u = msd_sort_unique<L, COUNTED>(c, &ka, &kb, &pa, &pb, n, nbits, cmax, dupf * hint_mult,
-                                             nullptr, distinct);
+    SortRequest<L> rq;
+    rq.distinct = distinct;
+    uint64_t u = msd_sort_unique<L, COUNTED>(c, &ka, &kb, &pa, &pb, n, nbits, cmax, dupf * hint_mult, rq);
     std::vector<Key<L>> got(u);
     std::vector<uint32_t> gc(u);
     HIP_CHECK(hipMemcpy(got.data(), ka, u * sizeof(Key<L>), hipMemcpyDeviceToHost));

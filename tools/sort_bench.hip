@@ -90,16 +90,16 @@ int main(int argc, char **argv) {
         HIP_CHECK(hipStreamSynchronize(c.stream));
         Key<1> *ka = a, *kb = b;
         uint32_t *nv = nullptr;
-        c.radix_ms = 0;
-        c.radix_launches = 0;
-        c.radix_bytes = 0;
+        c.build.radix_ms = 0;
+        c.build.radix_launches = 0;
+        c.build.radix_bytes = 0;
         double t0 = now_ms();
         radix_sort<1, false>(c, &ka, &kb, &nv, &nv, n, 62, true);
         HIP_CHECK(hipStreamSynchronize(c.stream));
         double t1 = now_ms();
         printf("mtg    : total %.3f ms, %lu passes, avg pass %.3f ms = %.0f GB/s\n", t1 - t0,
-               (unsigned long)c.radix_launches, c.radix_ms / c.radix_launches,
-               gb / (c.radix_ms / c.radix_launches) * 1e3);
+               (unsigned long)c.build.radix_launches, c.build.radix_ms / c.build.radix_launches,
+               gb / (c.build.radix_ms / c.build.radix_launches) * 1e3);
         std::vector<uint64_t> h(1 << 20);
         HIP_CHECK(hipMemcpy(h.data(), ka, h.size() * 8, hipMemcpyDeviceToHost));
         bool ok = true;
@@ -116,19 +116,19 @@ int main(int argc, char **argv) {
             HIP_CHECK(hipStreamSynchronize(c.stream));
             Key<1> *ka = a, *kb = b;
             uint32_t *nv = nullptr;
-            c.radix_ms = 0;
-            c.radix_launches = 0;
-            c.radix_bytes = 0;
-            c.track_partition = true;
+            c.build.radix_ms = 0;
+            c.build.radix_launches = 0;
+            c.build.radix_bytes = 0;
+            SortRequest<1> rq;
+            rq.track_partition = true;
             double t0 = now_ms();
-            uint64_t u = msd_sort_unique<1, false>(c, &ka, &kb, &nv, &nv, n, 62, 0, dupf);
+            uint64_t u = msd_sort_unique<1, false>(c, &ka, &kb, &nv, &nv, n, 62, 0, dupf, rq);
             HIP_CHECK(hipStreamSynchronize(c.stream));
             double t1 = now_ms();
-            c.track_partition = false;
             printf("msd dup=%d: total %.3f ms, unique %lu, %lu partition passes avg %.3f ms = %.0f GB/s\n",
-                   dupf, t1 - t0, (unsigned long)u, (unsigned long)c.radix_launches,
-                   c.radix_ms / std::max<uint64_t>(1, c.radix_launches),
-                   c.radix_launches ? c.radix_bytes / c.radix_ms / 1e6 : 0.0);
+                   dupf, t1 - t0, (unsigned long)u, (unsigned long)c.build.radix_launches,
+                   c.build.radix_ms / std::max<uint64_t>(1, c.build.radix_launches),
+                   c.build.radix_launches ? c.build.radix_bytes / c.build.radix_ms / 1e6 : 0.0);
             std::vector<uint64_t> h(1 << 20);
             HIP_CHECK(hipMemcpy(h.data(), ka, h.size() * 8, hipMemcpyDeviceToHost));
             bool ok = true;
