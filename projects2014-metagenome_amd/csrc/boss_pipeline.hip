@@ -41,6 +41,7 @@
 #include "radix_sort.hpp"
 #include "ctx.hpp"
 #include "sort_unique.hpp"
+#include "dummy_stage.hpp"
 
 namespace mtg {
 
@@ -92,14 +93,7 @@ static uint64_t stage_extract(Ctx &c, unsigned K, bool canonical, uint32_t cmax,
             in.seq, in.seq_len, K, cmode(c, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax,
             nullptr, nullptr, tcnt, nullptr, nullptr, 0);
         HIP_CHECK(hipGetLastError());
-        uint32_t ep;
-        const uint64_t st = ceil_div(tiles, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(
-            tcnt, tiles, toff, desc, ep, &c.small->counter, &c.small->error);
-        HIP_CHECK(hipGetLastError());
-        N = read_u64(c, (const unsigned long long *)(toff + tiles));
+        N = scan_counts_total(c, tcnt, tiles, toff);
         extract_kernel<L2, COUNTED, false><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(
             in.seq, in.seq_len, K, cmode(c, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax,
             *ka, *ca, nullptr, toff, nullptr, 0);
@@ -450,16 +444,7 @@ static uint64_t fused_pass_b_spec(Ctx &c, unsigned K, bool canonical, const Buil
                                                                (float)A.sample_factor, T2, caps, c.knobs.spec_l1_tiny,
                                                                c.knobs.spec_l1_slack);
     HIP_CHECK(hipGetLastError());
-    {
-        uint32_t ep;
-        const uint64_t st = ceil_div(nseg, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(caps, nseg, sst, desc, ep, &c.small->counter,
-                                                                          &c.small->error);
-        HIP_CHECK(hipGetLastError());
-    }
-    const uint64_t C1 = read_u64(c, (const unsigned long long *)(sst + nseg));
+    const uint64_t C1 = scan_counts_total(c, caps, nseg, sst);
     if (C1 % T2) throw std::logic_error("spec level 1: segments not tile-aligned");
     {  // the padded array must fit next to everything else
         const uint64_t fr = c.ws.free_bytes();
@@ -705,13 +690,7 @@ static uint64_t collect_ranges(Ctx &c, unsigned K, bool canonical, uint32_t cmax
         range_tile_counts_kernel<<<dim3((unsigned)ceil_div(tiles, 4)), dim3(256), 0, c.stream>>>(tbins, tiles, sel,
                                                                                                  tcnt);
         HIP_CHECK(hipGetLastError());
-        uint32_t ep;
-        const uint64_t st = ceil_div(tiles, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(tcnt, tiles, toff, desc, ep,
-                                                                          &c.small->counter, &c.small->error);
-        HIP_CHECK(hipGetLastError());
+        scan_counts(c, tcnt, tiles, toff);
         range_write_kernel<L2, COUNTED><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(
             in.seq, in.seq_len, K, both, in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, sel, toff, ka, ca);
         HIP_CHECK(hipGetLastError());
@@ -1071,12 +1050,7 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
                     const uint64_t nbk = 1ull << rc_hist_bits;
                     uint64_t *st = (uint64_t *)c.ws.get(Workspace::RC_L1START, (nbk + 1) * 8);
                     auto *cur = (unsigned long long *)c.ws.get(Workspace::RC_L1CUR, nbk * 8);
-                    uint32_t ep;
-                    uint64_t *desc = acquire_desc(c, 1, &ep);
-                    HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-                    scan_counts_kernel<<<dim3(1), dim3(512), 0, c.stream>>>(rc_hist, nbk, st, desc, ep, &c.small->counter,
-                                                                           &c.small->error);
-                    HIP_CHECK(hipGetLastError());
+                    scan_counts(c, rc_hist, nbk, st);  // fuse: rc_hist_bits <= 9, one block
                     HIP_CHECK(hipMemcpyAsync(cur, st, nbk * 8, hipMemcpyDeviceToDevice, c.stream));
                     rc_partition_gapped_kernel<L2><<<dim3((unsigned)xcd_grid(tiles)), dim3(512), 0, c.stream>>>(
                         (const K2 *)c.build.gap.keys, c.build.gap.bstart, c.build.gap.ustart, tile_g, c.build.gap.nb, U, K, rc_hist_bits, cur,
@@ -1127,179 +1101,36 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
     return Urc;
 }
 
-// LSD sort + unique of the raw dummy k-mers da[0..Draw) (db is the ping-pong buffer); returns
-// D and leaves the distinct dummies in *dk.  (An MSD sort of the dummies, planned for the 5-of-8
-// value density of lifted chars and with a read-before-CAS hash for their repeated keys, measured
-// 24.5 vs 7.5 ms per cfg2 step and 24.9 vs 0.51 s per cfg3 step: groups of the $-padded source
-// levels overflow the LDS tables and fall back.)
-// the dense-rank dummy sort (boss_kernels.hpp: dummy_rank): `ranks` (u64 view of one of the two
-// Draw-key buffers xa / xb) sorted + deduplicated, the distinct ranks decoded to lifted keys in
-// whichever buffer does not hold them (both hold Draw lifted keys); returns D, *dk = the keys
-template <int L3, int LR = 1>
-static uint64_t sort_unique_dummy_ranks(Ctx &c, unsigned kb, Key<L3> *xa, Key<L3> *xb, Key<LR> *ranks, uint64_t Draw,
-                                        Key<L3> **dk) {
-    static_assert(sizeof(Key<LR>) <= sizeof(Key<L3>), "the rank buffers are the lifted key buffers");
-    Key<LR> *ra = ranks, *rb = (void *)ranks == (void *)xa ? (Key<LR> *)xb : (Key<LR> *)xa;
-    uint32_t *nv = nullptr;
-    const unsigned nbits = dummy_rank_bits(kb);
-    // (the real k-mers' MSD partition + LDS-hash unique on these ranks: dummy stage 4.4 -> 6.8 ms)
-    radix_sort<LR, false>(c, &ra, &rb, &nv, &nv, Draw, nbits, false, true);  // (dense ranks: the low digit varies)
-    reset_small(c);
-    const uint64_t ut = ceil_div(Draw, 2048);
-    uint32_t udesc_ep;
-    uint64_t *udesc = acquire_desc(c, ut, &udesc_ep);
-    unique_kernel<LR, false><<<dim3((unsigned)ut), dim3(256), 0, c.stream>>>(
-        ra, nullptr, Draw, rb, nullptr, udesc, udesc_ep, &c.small->counter, &c.small->total, &c.small->error);
-    HIP_CHECK(hipGetLastError());
-    Key<L3> *outk = (void *)rb == (void *)xa ? xb : xa;
-    // (a block per 256 dummies up to 16384 blocks, each a contiguous chunk; the grid is sized for Draw and the
-    // kernel reads D from the device, so the copy of D to the host overlaps the decode)
-    dummy_decode_kernel<L3, LR><<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(Draw, 256), 16384))),
-                                  dim3(256), 0, c.stream>>>(rb, 0, kb, outk, &c.small->total);
-    HIP_CHECK(hipGetLastError());
-    const uint64_t D = read_u64(c, &c.small->total);
-    *dk = outk;
-    return D;
+// the widths a build counts in: k-mer counts saturate at cmax (cbits wide), the chunk's weights at wmax
+struct CountWidths {
+    unsigned cbits;
+    uint32_t cmax, wmax;
+};
+static CountWidths count_widths(unsigned bits) {
+    const unsigned cbits = bits <= 8 ? 8 : bits <= 16 ? 16 : 32;
+    return {cbits, cbits == 8 ? 0xFFu : cbits == 16 ? 0xFFFFu : 0xFFFFFFFFu,
+            bits >= 32 ? 0xFFFFFFFFu : (uint32_t)((1ull << bits) - 1)};
 }
 
-// sort + unique of the lifted dummy keys da[0..Draw) (db is the ping-pong buffer); returns D and
-// leaves the distinct dummies in *dk.  For k <= 30 they are sorted as dense u64 ranks (8 LSD passes
-// of 8-byte keys instead of 12 of 16-byte ones); otherwise, or when a key is not of the dummy shape,
-// by an LSD sort of the lifted keys.  (An MSD sort of the dummies, planned for the 5-of-8 value
-// density of lifted chars and with a read-before-CAS hash for their repeated keys, measured 24.5 vs
-// 7.5 ms per cfg2 step and 24.9 vs 0.51 s per cfg3 step: groups of the $-padded source levels
-// overflow the LDS tables and fall back.)
-template <int L3>
-static uint64_t sort_unique_dummies(Ctx &c, unsigned K, Key<L3> *da, Key<L3> *db, uint64_t Draw,
-                                    Key<L3> **dk) {
-    uint64_t D = 0;
-    uint32_t *nv = nullptr;
-    const unsigned kb = K - 1;
-    const int LR = dummy_rank_limbs(kb);
-    if (c.knobs.dummy_ranks && kb >= 1 && LR && (LR == 1 || L3 >= 2) && Draw) {
-        HIP_CHECK(hipMemsetAsync(&c.small->bad_dummy, 0, 4, c.stream));
-        const unsigned g = (unsigned)std::min<uint64_t>(ceil_div(Draw, 256), 16384);
-        if (LR == 1)
-            dummy_encode_kernel<L3, 1><<<dim3(g), dim3(256), 0, c.stream>>>(da, Draw, kb, (Key<1> *)db, &c.small->bad_dummy);
-        else
-            dummy_encode_kernel<L3, 2><<<dim3(g), dim3(256), 0, c.stream>>>(da, Draw, kb, (Key<2> *)db, &c.small->bad_dummy);
-        HIP_CHECK(hipGetLastError());
-        uint32_t bad = 0;
-        HIP_CHECK(hipMemcpyAsync(&bad, &c.small->bad_dummy, 4, hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-        if (!bad) {
-            if (LR == 1) return sort_unique_dummy_ranks<L3, 1>(c, kb, da, db, (Key<1> *)db, Draw, dk);
-            if constexpr (L3 >= 2) return sort_unique_dummy_ranks<L3, 2>(c, kb, da, db, (Key<2> *)db, Draw, dk);
-        }
-        if (c.knobs.debug) fprintf(stderr, "[mtg debug] dummy keys outside the rank shape: lifted sort\n");
-    }
-    {
-        radix_sort<L3, false>(c, &da, &db, &nv, &nv, Draw, 3 * K, false);
-        reset_small(c);
-        const uint64_t ut = ceil_div(Draw, 2048);
-        uint32_t udesc_ep;
-        uint64_t *udesc = acquire_desc(c, ut, &udesc_ep);
-        unique_kernel<L3, false><<<dim3((unsigned)ut), dim3(256), 0, c.stream>>>(
-            da, nullptr, Draw, db, nullptr, udesc, udesc_ep, &c.small->counter, &c.small->total,
-            &c.small->error);
-        HIP_CHECK(hipGetLastError());
-        D = read_u64(c, &c.small->total);
-    }
-    *dk = db;
-    return D;
-}
-
-// K5/K6 on one device: dummy sinks and sources (all levels) of the sorted real edges ka[0..R)
-template <int L2, int L3>
-static uint64_t stage_dummies_local(Ctx &c, unsigned K, const Key<L2> *ka, uint64_t R, Key<L3> **dk) {
-    using K3 = Key<L3>;
-    const unsigned k = K - 1;
-    const unsigned B = bucket_bits<L2>(R, 2 * K);
-    const unsigned bshift = 2 * K - B;
-    const uint64_t nb = 1ull << B;
-    uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::BUCKETS, (nb + 2) * 8);
-    if (!(bidx_valid(c, ka, R) && c.build.bidx_shift == bshift && c.build.bidx == bstart)) {
-        const uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(R + 1, 256), 8192));
-        bucket_index_kernel<L2><<<dim3((unsigned)g), dim3(256), 0, c.stream>>>(ka, R, bshift, nb, bstart);
-        HIP_CHECK(hipGetLastError());
-        note_bucket_index(c, ka, R, bstart, bshift);
-    }
-    uint8_t *flags = (uint8_t *)c.ws.get(Workspace::FLAGS, R + 1);
-    uint8_t *in_flag = (uint8_t *)c.ws.get(Workspace::INFLAG, R + 1);
-    const uint64_t wtiles = ceil_div(R, DummyTraits<L2>::WTILE);
-    uint32_t *tcnt = (uint32_t *)c.ws.get(Workspace::DTCNT, (wtiles + 1) * 4);
-    uint64_t *toff = (uint64_t *)c.ws.get(Workspace::DTOFF, (wtiles + 1) * 8);
-    uint64_t Draw = 0;
-    // the dense-rank path writes the source levels with <= DUMMY_BITMAP_M real chars as bits of a bitmap
-    // (dummy_write_kernel), so the count pass counts kbig levels per source
-    const bool bitmap_path = L2 == 1 && c.knobs.dummy_ranks && c.knobs.dummy_bitmap && k >= 1 && k <= 30;
-    const unsigned ks = std::min<unsigned>(k, DUMMY_BITMAP_M + 1), kbig = bitmap_path ? k - ks : k;
-    if (R) {
-        HIP_CHECK(hipMemsetAsync(in_flag, 0, R, c.stream));
-        dummy_sink_kernel<L2><<<dim3((unsigned)ceil_div(R, DummyTraits<L2>::TILE)), dim3(256), 0,
-                                c.stream>>>(ka, R, K, bstart, bshift, flags, in_flag);
-        HIP_CHECK(hipGetLastError());
-        dummy_count_kernel<<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(flags, in_flag, R, kbig, tcnt);
-        HIP_CHECK(hipGetLastError());
-        uint32_t ep;
-        const uint64_t st = ceil_div(wtiles, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(
-            tcnt, wtiles, toff, desc, ep, &c.small->counter, &c.small->error);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(&Draw, toff + wtiles, 8, hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-    }
-    *dk = nullptr;
-    if constexpr (L2 == 1) {
-        if (bitmap_path) {  // written as dense ranks: no lifted keys until the decode
-            const uint64_t nbits = dummy_bitmap_base(ks), nwords = ceil_div(nbits, 32);
-            uint32_t *bm = (uint32_t *)c.ws.get(Workspace::DBITMAP, nwords * 4);
-            HIP_CHECK(hipMemsetAsync(bm, 0, nwords * 4, c.stream));
-            const uint64_t cap = Draw + nbits;  // u64 ranks: the written ones, then at most every bit
-            K3 *da = (K3 *)c.ws.get(Workspace::DA, cap * sizeof(K3));
-            K3 *db = (K3 *)c.ws.get(Workspace::DB, cap * sizeof(K3));
-            if (R) {
-                dummy_write_kernel<L2, L3, true><<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(
-                    ka, flags, in_flag, R, K, toff, da, kbig, bm);
-                HIP_CHECK(hipGetLastError());
-            }
-            HIP_CHECK(hipMemcpyAsync(&c.small->total, &Draw, 8, hipMemcpyHostToDevice, c.stream));
-            dummy_bitmap_ranks_kernel<<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(nwords, 256), 4096))),
-                                        dim3(256), 0, c.stream>>>(bm, nwords, k, ks, (uint64_t *)da, &c.small->total);
-            HIP_CHECK(hipGetLastError());
-            const uint64_t Dall = read_u64(c, &c.small->total);  // (also orders the copy of the host local)
-            if (c.knobs.debug)
-                fprintf(stderr, "[mtg debug] dummies: %lu written + %lu from the bitmap (%u levels per source)\n",
-                        (unsigned long)Draw, (unsigned long)(Dall - Draw), ks);
-            if (!Dall) return 0;
-            return sort_unique_dummy_ranks<L3>(c, k, da, db, (Key<1> *)da, Dall, dk);
-        }
-    }
-    if (!Draw) return 0;
-    K3 *da = (K3 *)c.ws.get(Workspace::DA, Draw * sizeof(K3));
-    K3 *db = (K3 *)c.ws.get(Workspace::DB, Draw * sizeof(K3));
-    if constexpr (L2 == 1) {
-        if (c.knobs.dummy_ranks && k <= 30) {  // written as dense ranks: no lifted keys until the decode
-            dummy_write_kernel<L2, L3, true><<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(ka, flags, in_flag,
-                                                                                                  R, K, toff, da);
-            HIP_CHECK(hipGetLastError());
-            return sort_unique_dummy_ranks<L3>(c, k, da, db, (Key<1> *)da, Draw, dk);
-        }
-    }
-    if constexpr (L2 <= 2 && L3 >= 2) {
-        if (c.knobs.dummy_ranks && dummy_rank_limbs(k) == 2) {  // 30 < k <= 62: dense u128 ranks (configs[2]: k = 62)
-            dummy_write_kernel<L2, L3, true, 2><<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(ka, flags, in_flag,
-                                                                                                     R, K, toff, da);
-            HIP_CHECK(hipGetLastError());
-            return sort_unique_dummy_ranks<L3, 2>(c, k, da, db, (Key<2> *)da, Draw, dk);
-        }
-    }
-    dummy_write_kernel<L2, L3><<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(ka, flags, in_flag, R, K,
-                                                                                    toff, da);
-    HIP_CHECK(hipGetLastError());
-    return sort_unique_dummies<L3>(c, K, da, db, Draw, dk);
+// the timing fields every in-HBM build reports, from the event marks at the end of its stages
+struct StageMarks {
+    int start, extract, sort, unique, rc, dummy, merge, emit;
+};
+static void fill_timings(Ctx &c, EventTimer &tm, const StageMarks &m, uint64_t n_rows) {
+    mtg_boss_timings &T = c.timings;
+    T.n_rows = n_rows;
+    T.extract_ms = tm.ms(m.start, m.extract);
+    T.sort_ms = tm.ms(m.extract, m.sort);
+    T.unique_ms = tm.ms(m.sort, m.unique);
+    T.rc_ms = tm.ms(m.unique, m.rc);
+    T.dummy_ms = tm.ms(m.rc, m.dummy);
+    T.merge_ms = tm.ms(m.dummy, m.merge);
+    T.emit_ms = tm.ms(m.merge, m.emit);
+    T.total_ms = tm.ms(m.start, m.emit);
+    T.radix_launches = c.build.radix_launches;
+    T.radix_pass_ms = c.build.radix_launches ? c.build.radix_ms / c.build.radix_launches : 0;
+    T.radix_bytes = c.build.radix_launches ? c.build.radix_bytes / c.build.radix_launches : 0;
+    T.peak_bytes = c.ws.held();
 }
 
 // K8 over a sorted lifted stream sk[0..M) (+ counts): initialize_chunk (boss_chunk.cpp:32-133),
@@ -1365,7 +1196,7 @@ static void stage_merge_emit(Ctx &c, EventTimer &tm, int *ev_merge, unsigned k, 
                              uint64_t D, bool root, BuildOutput *out) {
     using K3 = Key<L3>;
     const unsigned K = k + 1;
-    const uint32_t wmax = bits >= 32 ? 0xFFFFFFFFu : (uint32_t)((1ull << bits) - 1);
+    const uint32_t wmax = count_widths(bits).wmax;
     const uint64_t M = (root ? 1 : 0) + R + D;
     if (c.knobs.fused_emit && !c.knobs.emit_slow && M) {
         // K7 + K8 without the merged stream (split_emit_kernel): the dummies' output rows from
@@ -1434,8 +1265,8 @@ static void run_pipeline(Ctx &c, unsigned k, bool canonical, unsigned bits,
                          const BuildInput &in, BuildOutput *out) {
     using K2 = Key<L2>;
     const unsigned K = k + 1;
-    const unsigned cbits = bits <= 8 ? 8 : bits <= 16 ? 16 : 32;
-    const uint32_t cmax = cbits == 8 ? 0xFFu : cbits == 16 ? 0xFFFFu : 0xFFFFFFFFu;
+    const unsigned cbits = count_widths(bits).cbits;
+    const uint32_t cmax = count_widths(bits).cmax;
     mtg_boss_timings &T = c.timings;
     T = mtg_boss_timings{};
     T.world = 1;
@@ -1556,19 +1387,7 @@ static void run_pipeline(Ctx &c, unsigned k, bool canonical, unsigned bits,
     check_error_word(c);
     HIP_CHECK(hipStreamSynchronize(c.stream));
 
-    T.n_rows = out->n;
-    T.extract_ms = tm.ms(ev_start, ev_extract);
-    T.sort_ms = tm.ms(ev_extract, ev_sort);
-    T.unique_ms = tm.ms(ev_sort, ev_unique);
-    T.rc_ms = tm.ms(ev_unique, ev_rc);
-    T.dummy_ms = tm.ms(ev_rc, ev_dummy);
-    T.merge_ms = tm.ms(ev_dummy, ev_merge);
-    T.emit_ms = tm.ms(ev_merge, ev_emit);
-    T.total_ms = tm.ms(ev_start, ev_emit);
-    T.radix_launches = c.build.radix_launches;
-    T.radix_pass_ms = c.build.radix_launches ? c.build.radix_ms / c.build.radix_launches : 0;
-    T.radix_bytes = c.build.radix_launches ? c.build.radix_bytes / c.build.radix_launches : 0;
-    T.peak_bytes = c.ws.held();
+    fill_timings(c, tm, {ev_start, ev_extract, ev_sort, ev_unique, ev_rc, ev_dummy, ev_merge, ev_emit}, out->n);
 }
 
 // ------------------------------------------------------------------------ multi-GPU pipeline
@@ -1798,13 +1617,7 @@ static std::vector<uint64_t> route(Ctx &c, const Dist &d, const Key<L> *in, uint
     route_count_kernel<L, MODE><<<dim3((unsigned)ntiles), dim3(RT_BLOCK), 0, c.stream>>>(
         in, n, K, pshift, pbits, db, (uint32_t)P, tcnt, ntiles);
     HIP_CHECK(hipGetLastError());
-    uint32_t ep;
-    const uint64_t st = ceil_div(P * ntiles, 4096);
-    uint64_t *desc = acquire_desc(c, st, &ep);
-    HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-    scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(tcnt, P * ntiles, toff, desc, ep,
-                                                                      &c.small->counter, &c.small->error);
-    HIP_CHECK(hipGetLastError());
+    scan_counts(c, tcnt, P * ntiles, toff);
     route_write_kernel<L, MODE><<<dim3((unsigned)ntiles), dim3(RT_BLOCK), 0, c.stream>>>(
         in, n, K, pshift, pbits, db, (uint32_t)P, toff, ntiles, out, in_v, out_v);
     HIP_CHECK(hipGetLastError());
@@ -1814,6 +1627,173 @@ static std::vector<uint64_t> route(Ctx &c, const Dist &d, const Key<L> *in, uint
     HIP_CHECK(hipMemcpyAsync(soff.data(), g, (P + 1) * 8, hipMemcpyDeviceToHost, c.stream));
     HIP_CHECK(hipStreamSynchronize(c.stream));
     return soff;
+}
+
+// ------------------------------------------------- multi-GPU: K5/K6 (shared pieces in dummy_stage.hpp)
+
+// the dummy keys src[0..n) routed to the owners of their lifted prefixes and exchanged: the received keys
+// in *recv (the DRECV slot), their count returned
+template <int L3>
+static uint64_t exchange_dummies(Ctx &c, Dist &d, unsigned K, const Key<L3> *src, uint64_t n,
+                                 const std::vector<uint64_t> &bounds, Key<L3> **recv) {
+    using K3 = Key<L3>;
+    K3 *ssend = (K3 *)c.ws.get(Workspace::DSEND, std::max<uint64_t>(n, 1) * sizeof(K3));
+    std::vector<std::vector<uint64_t>> doff(1);
+    doff[0] = route<L3, 1>(c, d, src, n, K, 3 * K - 3 * d.m, 3 * d.m, lifted_bounds(bounds, d.m), ssend);
+    uint32_t *unused_c = nullptr;
+    const K3 *darr[1] = {ssend};
+    return exchange_runs<K3>(c, d, 1, darr, nullptr, doff, Workspace::DRECV, Workspace::XAC, recv, &unused_c);
+}
+
+// the pulled sink join (dist_kernels.hpp: pull_bounds_kernel): every rank sends each owner the slices of
+// its edges whose nodes the owner's edges target, the owner runs the single build's join
+// (dummy_sink_kernel) of its edges against them and returns an in-edge byte per received edge; sinks and
+// sources are then written like the single build's and routed to their owners
+template <int L2, int L3>
+static uint64_t dummies_dist_pulled(Ctx &c, Dist &d, unsigned K, const Key<L2> *E, uint64_t R,
+                                    const std::vector<uint64_t> &bounds, Tracer &tr, Key<L3> **dk) {
+    using K2 = Key<L2>;
+    using K3 = Key<L3>;
+    uint8_t *flags = (uint8_t *)c.ws.get(Workspace::FLAGS, R + 1);
+    std::vector<std::vector<uint64_t>> qoff(4, std::vector<uint64_t>(d.P + 1, 0));
+    std::vector<uint64_t> cstart(5, R);
+    cstart[0] = 0;
+    if (R) {
+        uint64_t *db = (uint64_t *)c.ws.get(Workspace::BOUNDS, (d.P + 1) * 8);
+        uint64_t *g = (uint64_t *)c.ws.get(Workspace::XGATHER, 4 * (d.P + 1) * 8);
+        HIP_CHECK(hipMemcpyAsync(db, bounds.data(), (d.P + 1) * 8, hipMemcpyHostToDevice, c.stream));
+        pull_bounds_kernel<L2><<<dim3((unsigned)ceil_div(4 * (d.P + 1), 256)), dim3(256), 0, c.stream>>>(
+            E, R, db, (uint32_t)d.P, K, d.m, g);
+        HIP_CHECK(hipGetLastError());
+        std::vector<uint64_t> pos(4 * (d.P + 1));
+        HIP_CHECK(hipMemcpyAsync(pos.data(), g, pos.size() * 8, hipMemcpyDeviceToHost, c.stream));
+        HIP_CHECK(hipStreamSynchronize(c.stream));  // bounds / pos are host locals
+        for (int cl = 0; cl < 4; ++cl) {
+            cstart[cl] = pos[cl * (d.P + 1)];
+            for (int j = 0; j <= d.P; ++j) qoff[cl][j] = pos[cl * (d.P + 1) + j] - cstart[cl];
+        }
+        if (cstart[0] != 0 || pos[3 * (d.P + 1) + d.P] != R)
+            throw std::logic_error("pulled join: the class slices do not cover the edges");
+    }
+    tr("pull bounds", R);
+    K2 *qr;
+    uint32_t *unused_c = nullptr;
+    const K2 *qarr[4] = {E + cstart[0], E + cstart[1], E + cstart[2], E + cstart[3]};
+    std::vector<uint64_t> qruns;
+    const uint64_t nq = exchange_runs<K2>(c, d, 4, qarr, nullptr, qoff, Workspace::QRECV, Workspace::XAC, &qr,
+                                          &unused_c, &qruns);
+    tr("exchange pulled edges", nq);
+    // the received edges are sorted (array-major = by top char, then by source rank = key order)
+    const unsigned QB = bucket_bits<L2>(nq, 2 * K);
+    const unsigned qshift = 2 * K - QB;
+    uint64_t *qstart = (uint64_t *)c.ws.get(Workspace::QINDEX, ((1ull << QB) + 2) * 8);
+    bucket_index<L2>(c, qr, nq, qshift, 1ull << QB, qstart);
+    uint8_t *qin = (uint8_t *)c.ws.get(Workspace::QFLAG, nq + 1);
+    if (nq) HIP_CHECK(hipMemsetAsync(qin, 0, nq, c.stream));
+    if (R) {
+        dummy_sink_kernel<L2><<<dim3((unsigned)ceil_div(R, DummyTraits<L2>::TILE)), dim3(256), 0, c.stream>>>(
+            E, R, K, qstart, qshift, flags, qin, qr, nq);
+        HIP_CHECK(hipGetLastError());
+    }
+    tr("pulled join", nq);
+    // exchange back: the in-edge byte of every received edge to its sender, where the 4 x P pieces
+    // land aligned with the sender's edge array (its classes in order, each by owner)
+    std::vector<std::vector<uint64_t>> boff(4, std::vector<uint64_t>(d.P + 1, 0));
+    const uint8_t *barr[4];
+    for (int cl = 0; cl < 4; ++cl) {
+        const uint64_t b0 = qruns[cl * d.P];
+        barr[cl] = qin + b0;
+        for (int i = 0; i < d.P; ++i) boff[cl][i] = qruns[cl * d.P + i] - b0;
+        boff[cl][d.P] = qruns[(cl + 1) * d.P] - b0;  // the next class's first run (or the total)
+    }
+    uint8_t *in_flag;
+    uint32_t *unused_b = nullptr;
+    const uint64_t nback = exchange_runs<uint8_t>(c, d, 4, barr, nullptr, boff, Workspace::INFLAG, Workspace::XAC,
+                                                  &in_flag, &unused_b);
+    if (nback != R) throw std::logic_error("pulled join: in-edge bytes do not match the edges");
+    tr("exchange in-edge bytes", nback);
+    // the bucket index of the owned edges, for the split emit's dummy ranks (unless the fused rc
+    // merge wrote it)
+    if (!bidx_valid(c, E, R)) real_bucket_index<L2>(c, E, R, K, true);
+    // sinks (lift(to_next(x, 0)) with label $) and sources of every level, as the single build writes
+    // them, routed to the owners of their lifted prefixes
+    uint64_t nraw = 0;
+    K3 *src = write_sources<L2, L3>(c, E, flags, in_flag, R, K, K - 1, &nraw);
+    tr("sinks + sources", nraw);
+    K3 *drecv;
+    const uint64_t Draw = exchange_dummies<L3>(c, d, K, src, nraw, bounds, &drecv);
+    tr("route + exchange dummies", Draw);
+    if (!Draw) return 0;
+    K3 *da = (K3 *)c.ws.get(Workspace::DA, Draw * sizeof(K3));
+    K3 *db = (K3 *)c.ws.get(Workspace::DB, Draw * sizeof(K3));
+    HIP_CHECK(hipMemcpyAsync(da, drecv, Draw * sizeof(K3), hipMemcpyDeviceToDevice, c.stream));
+    const uint64_t D = sort_unique_dummies<L3>(c, K, da, db, Draw, dk);
+    tr("dummy sort", D);
+    return D;
+}
+
+// the queried sink join: the sink query t = to_next(x, 0) of every owned edge goes to the owner of t,
+// which marks the edges it hits and keeps the sinks of the queries that miss; the sources of the owned
+// edges no query hit are routed to the owners of their lifted prefixes
+template <int L2, int L3>
+static uint64_t dummies_dist_queried(Ctx &c, Dist &d, unsigned K, const Key<L2> *E, uint64_t R,
+                                     const std::vector<uint64_t> &bounds, Tracer &tr, Key<L3> **dk) {
+    using K2 = Key<L2>;
+    using K3 = Key<L3>;
+    const BucketIndex bi = real_bucket_index<L2>(c, E, R, K, true);
+    uint8_t *flags = (uint8_t *)c.ws.get(Workspace::FLAGS, R + 1);
+    uint8_t *in_flag = (uint8_t *)c.ws.get(Workspace::INFLAG, R + 1);
+    first_flags<L2>(c, E, R, flags, in_flag);
+    std::vector<std::vector<uint64_t>> qoff(4, std::vector<uint64_t>(d.P + 1, 0));
+    std::vector<uint64_t> cstart(5, 0), pos(4 * (d.P + 1));
+    K2 *qs = split_queries<L2>(c, E, R, K, (uint32_t)d.P, bounds, d.shift2, cstart.data(), pos.data());
+    if (R) {  // relative to the class start; the last owner ends at its class end
+        for (int cl = 0; cl < 4; ++cl)
+            for (int j = 0; j <= d.P; ++j) qoff[cl][j] = pos[cl * (d.P + 1) + j] - cstart[cl];
+        for (int cl = 0; cl < 4; ++cl) qoff[cl][d.P] = cstart[cl + 1] - cstart[cl];
+    }
+    tr("first flags + split q", R);
+    K2 *qr;
+    uint32_t *unused_c = nullptr;
+    const K2 *qarr[4] = {qs + cstart[0], qs + cstart[1], qs + cstart[2], qs + cstart[3]};
+    const uint64_t nq = exchange_runs<K2>(c, d, 4, qarr, nullptr, qoff, Workspace::QRECV, Workspace::XAC, &qr,
+                                          &unused_c);
+    tr("exchange q", nq);
+    // sinks of the missed queries: count + scan now, written once the buffer is sized
+    const SinkJoin sj = answer_queries<L2>(c, E, R, bi, qr, nq, in_flag, &tr);
+    tr("sink count", sj.nsink);
+    // sources of the owned edges (in_flag is complete: every rank's queries are answered)
+    uint64_t nsrc = 0;
+    K3 *src = write_sources<L2, L3>(c, E, flags, in_flag, R, K, K - 1, &nsrc);
+    tr("sources", nsrc);
+    K3 *drecv;
+    const uint64_t nsrc_in = exchange_dummies<L3>(c, d, K, src, nsrc, bounds, &drecv);
+    const uint64_t Draw = sj.nsink + nsrc_in;
+    tr("route + exchange src", nsrc_in);
+    if (!Draw) return 0;
+    K3 *da = (K3 *)c.ws.get(Workspace::DA, Draw * sizeof(K3));
+    K3 *db = (K3 *)c.ws.get(Workspace::DB, Draw * sizeof(K3));
+    if (sj.nsink) write_sinks<L2, L3>(c, K, qr, nq, sj, da);
+    if (nsrc_in)
+        HIP_CHECK(hipMemcpyAsync(da + sj.nsink, drecv, nsrc_in * sizeof(K3), hipMemcpyDeviceToDevice, c.stream));
+    tr("sink write", Draw);
+    const uint64_t D = sort_unique_dummies<L3>(c, K, da, db, Draw, dk);
+    tr("dummy sort", D);
+    return D;
+}
+
+// K5/K6 of the owned edges E[0..R): sink / in-edge queries to the target node's owner, sources to theirs;
+// returns D and leaves the distinct owned dummies in *dk
+template <int L2, int L3>
+static uint64_t stage_dummies_dist(Ctx &c, Dist &d, unsigned K, const Key<L2> *E, uint64_t R,
+                                   const std::vector<uint64_t> &bounds, Tracer &tr, Key<L3> **dk) {
+    if (d.P == 1) {  // one rank owns every target node: the single build's local join
+        const uint64_t D = stage_dummies_local<L2, L3>(c, K, E, R, dk);
+        tr("dummies (local)", D);
+        return D;
+    }
+    if (c.knobs.dist_pull && d.m + 1 <= K - 1) return dummies_dist_pulled<L2, L3>(c, d, K, E, R, bounds, tr, dk);
+    return dummies_dist_queried<L2, L3>(c, d, K, E, R, bounds, tr, dk);
 }
 
 // ------------------------------------------------- multi-GPU: the bounded-memory (batched) collect
@@ -1925,13 +1905,7 @@ static uint64_t collect_ranges_dist(Ctx &c, Dist &d, unsigned K, bool canonical,
             range_tile_counts_kernel<<<dim3((unsigned)ceil_div(tiles, 4)), dim3(256), 0, c.stream>>>(tbins, tiles, sel,
                                                                                                      tcnt);
             HIP_CHECK(hipGetLastError());
-            uint32_t ep;
-            const uint64_t st = ceil_div(tiles, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(tcnt, tiles, toff, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
+            scan_counts(c, tcnt, tiles, toff);
             range_write_kernel<L2, COUNTED><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(
                 in.seq, in.seq_len, K, both, in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, sel, toff, ka, ca);
             HIP_CHECK(hipGetLastError());
@@ -2690,15 +2664,8 @@ static bool dist_superkmers(Ctx &c, Dist &d, unsigned K, bool canonical, const B
             own, npos, in.seq, K, P, ntiles, tcnt, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
             nullptr);
         HIP_CHECK(hipGetLastError());
-        for (int half = 0; half < 2; ++half) {
-            uint32_t ep;
-            const uint64_t st = ceil_div(P * ntiles, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(
-                tcnt + half * P * ntiles, P * ntiles, half ? toffw : toff, desc, ep, &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-        }
+        for (int half = 0; half < 2; ++half)
+            scan_counts(c, tcnt + half * P * ntiles, P * ntiles, half ? toffw : toff);
         uint64_t *g = (uint64_t *)c.ws.get(Workspace::XGATHER, 2 * (P + 1) * 8);
         gather_strided_kernel<<<1, 256, 0, c.stream>>>(toff, ntiles, P + 1, g);
         gather_strided_kernel<<<1, 256, 0, c.stream>>>(toffw, ntiles, P + 1, g + P + 1);
@@ -2743,14 +2710,7 @@ static bool dist_superkmers(Ctx &c, Dist &d, unsigned K, bool canonical, const B
     if (per_read && nr) {
         uint64_t *wstart = (uint64_t *)c.ws.get(Workspace::SK_WOFF, (nr + 1) * 8);
         uint64_t *starts = (uint64_t *)c.ws.get(Workspace::SK_STARTS, nr * 8);
-        uint32_t ep;
-        const uint64_t st = ceil_div(nr, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(rnw, nr, wstart, desc, ep, &c.small->counter,
-                                                                          &c.small->error);
-        HIP_CHECK(hipGetLastError());
-        if (read_u64(c, (const unsigned long long *)(wstart + nr)) != nw)
+        if (scan_counts_total(c, rnw, nr, wstart) != nw)
             throw std::runtime_error("received super-k-mer words differ from their runs' word counts");
         const unsigned g = (unsigned)std::min<uint64_t>(ceil_div(nr, 256), 16384);
         sk_starts_kernel<<<dim3(g), dim3(256), 0, c.stream>>>(wstart, nr, starts);
@@ -2776,8 +2736,8 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
     using K2 = Key<L2>;
     using K3 = Key<L3>;
     const unsigned K = k + 1;
-    const unsigned cbits = bits <= 8 ? 8 : bits <= 16 ? 16 : 32;
-    const uint32_t cmax = cbits == 8 ? 0xFFu : cbits == 16 ? 0xFFFFu : 0xFFFFFFFFu;
+    const unsigned cbits = count_widths(bits).cbits;
+    const uint32_t cmax = count_widths(bits).cmax;
     mtg_boss_timings &T = c.timings;
     T = mtg_boss_timings{};
     HIP_CHECK(hipMemsetAsync(c.small, 0, sizeof(Small), c.stream));
@@ -2980,259 +2940,8 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
     const int ev_rc = tm.mark();
 
     // ---- K5/K6: sink / in-edge queries to the target node's owner, sources to theirs
-    const unsigned k_b = K - 1;
-    uint64_t D = 0;
     K3 *dk = nullptr;
-    if (d.P == 1) {  // one rank owns every target node: the single build's local join
-        D = stage_dummies_local<L2, L3>(c, K, E, R, &dk);
-        tr("dummies (local)", D);
-    } else if (c.knobs.dist_pull && d.m + 1 <= k_b) {
-        // the pulled sink join (dist_kernels.hpp: pull_bounds_kernel): every rank sends each owner the
-        // slices of its edges whose nodes the owner's edges target, the owner runs the single build's
-        // join (dummy_sink_kernel) of its edges against them and returns an in-edge byte per received
-        // edge; sinks and sources are then written like the single build's and routed to their owners
-        uint8_t *flags = (uint8_t *)c.ws.get(Workspace::FLAGS, R + 1);
-        std::vector<std::vector<uint64_t>> qoff(4, std::vector<uint64_t>(d.P + 1, 0));
-        std::vector<uint64_t> cstart(5, R);
-        cstart[0] = 0;
-        if (R) {
-            uint64_t *db = (uint64_t *)c.ws.get(Workspace::BOUNDS, (d.P + 1) * 8);
-            uint64_t *g = (uint64_t *)c.ws.get(Workspace::XGATHER, 4 * (d.P + 1) * 8);
-            HIP_CHECK(hipMemcpyAsync(db, bounds.data(), (d.P + 1) * 8, hipMemcpyHostToDevice, c.stream));
-            pull_bounds_kernel<L2><<<dim3((unsigned)ceil_div(4 * (d.P + 1), 256)), dim3(256), 0, c.stream>>>(
-                E, R, db, (uint32_t)d.P, K, d.m, g);
-            HIP_CHECK(hipGetLastError());
-            std::vector<uint64_t> pos(4 * (d.P + 1));
-            HIP_CHECK(hipMemcpyAsync(pos.data(), g, pos.size() * 8, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));  // bounds / pos are host locals
-            for (int cl = 0; cl < 4; ++cl) {
-                cstart[cl] = pos[cl * (d.P + 1)];
-                for (int j = 0; j <= d.P; ++j) qoff[cl][j] = pos[cl * (d.P + 1) + j] - cstart[cl];
-            }
-            if (cstart[0] != 0 || pos[3 * (d.P + 1) + d.P] != R)
-                throw std::logic_error("pulled join: the class slices do not cover the edges");
-        }
-        tr("pull bounds", R);
-        K2 *qr;
-        uint32_t *unused_c = nullptr;
-        const K2 *qarr[4] = {E + cstart[0], E + cstart[1], E + cstart[2], E + cstart[3]};
-        std::vector<uint64_t> qruns;
-        const uint64_t nq = exchange_runs<K2>(c, d, 4, qarr, nullptr, qoff, Workspace::QRECV, Workspace::XAC, &qr,
-                                              &unused_c, &qruns);
-        tr("exchange pulled edges", nq);
-        // the received edges are sorted (array-major = by top char, then by source rank = key order)
-        const unsigned QB = bucket_bits<L2>(nq, 2 * K);
-        const unsigned qshift = 2 * K - QB;
-        uint64_t *qstart = (uint64_t *)c.ws.get(Workspace::QINDEX, ((1ull << QB) + 2) * 8);
-        bucket_index<L2>(c, qr, nq, qshift, 1ull << QB, qstart);
-        uint8_t *qin = (uint8_t *)c.ws.get(Workspace::QFLAG, nq + 1);
-        if (nq) HIP_CHECK(hipMemsetAsync(qin, 0, nq, c.stream));
-        if (R) {
-            dummy_sink_kernel<L2><<<dim3((unsigned)ceil_div(R, DummyTraits<L2>::TILE)), dim3(256), 0, c.stream>>>(
-                E, R, K, qstart, qshift, flags, qin, qr, nq);
-            HIP_CHECK(hipGetLastError());
-        }
-        tr("pulled join", nq);
-        // exchange back: the in-edge byte of every received edge to its sender, where the 4 x P pieces
-        // land aligned with the sender's edge array (its classes in order, each by owner)
-        std::vector<std::vector<uint64_t>> boff(4, std::vector<uint64_t>(d.P + 1, 0));
-        const uint8_t *barr[4];
-        for (int cl = 0; cl < 4; ++cl) {
-            const uint64_t b0 = qruns[cl * d.P];
-            barr[cl] = qin + b0;
-            for (int i = 0; i < d.P; ++i) boff[cl][i] = qruns[cl * d.P + i] - b0;
-            boff[cl][d.P] = qruns[(cl + 1) * d.P] - b0;  // the next class's first run (or the total)
-        }
-        uint8_t *in_flag;
-        uint32_t *unused_b = nullptr;
-        const uint64_t nback = exchange_runs<uint8_t>(c, d, 4, barr, nullptr, boff, Workspace::INFLAG, Workspace::XAC,
-                                                      &in_flag, &unused_b);
-        if (nback != R) throw std::logic_error("pulled join: in-edge bytes do not match the edges");
-        tr("exchange in-edge bytes", nback);
-        // the bucket index of the owned edges, for the split emit's dummy ranks (unless the fused rc
-        // merge wrote it)
-        if (!bidx_valid(c, E, R)) {
-            const unsigned B = bucket_bits<L2>(R, 2 * K);
-            const unsigned bshift = 2 * K - B;
-            uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::BUCKETS, ((1ull << B) + 2) * 8);
-            bucket_index<L2>(c, E, R, bshift, 1ull << B, bstart);
-            note_bucket_index(c, E, R, bstart, bshift);
-        }
-        // sinks (lift(to_next(x, 0)) with label $) and sources of every level, as the single build writes
-        // them, routed to the owners of their lifted prefixes
-        const uint64_t wtiles = ceil_div(R, DummyTraits<L2>::WTILE);
-        uint32_t *tcnt = (uint32_t *)c.ws.get(Workspace::DTCNT, (wtiles + 1) * 4);
-        uint64_t *toff = (uint64_t *)c.ws.get(Workspace::DTOFF, (wtiles + 1) * 8);
-        uint64_t nraw = 0;
-        if (R) {
-            dummy_count_kernel<<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(flags, in_flag, R, k_b, tcnt);
-            HIP_CHECK(hipGetLastError());
-            uint32_t ep;
-            const uint64_t st = ceil_div(wtiles, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(tcnt, wtiles, toff, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-            nraw = read_u64(c, (const unsigned long long *)(toff + wtiles));
-        }
-        K3 *src = (K3 *)c.ws.get(Workspace::DSRC, std::max<uint64_t>(nraw, 1) * sizeof(K3));
-        if (nraw) {
-            dummy_write_kernel<L2, L3><<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(E, flags, in_flag, R, K,
-                                                                                            toff, src);
-            HIP_CHECK(hipGetLastError());
-        }
-        tr("sinks + sources", nraw);
-        K3 *ssend = (K3 *)c.ws.get(Workspace::DSEND, std::max<uint64_t>(nraw, 1) * sizeof(K3));
-        std::vector<std::vector<uint64_t>> doff(1);
-        doff[0] = route<L3, 1>(c, d, src, nraw, K, 3 * K - 3 * d.m, 3 * d.m, lifted_bounds(bounds, d.m), ssend);
-        K3 *drecv;
-        const K3 *darr[1] = {ssend};
-        const uint64_t Draw = exchange_runs<K3>(c, d, 1, darr, nullptr, doff, Workspace::DRECV, Workspace::XAC, &drecv,
-                                                &unused_c);
-        tr("route + exchange dummies", Draw);
-        if (Draw) {
-            K3 *da = (K3 *)c.ws.get(Workspace::DA, Draw * sizeof(K3));
-            K3 *db = (K3 *)c.ws.get(Workspace::DB, Draw * sizeof(K3));
-            HIP_CHECK(hipMemcpyAsync(da, drecv, Draw * sizeof(K3), hipMemcpyDeviceToDevice, c.stream));
-            D = sort_unique_dummies<L3>(c, K, da, db, Draw, &dk);
-            tr("dummy sort", D);
-        }
-    } else {
-        const unsigned B = bucket_bits<L2>(R, 2 * K);
-        const unsigned bshift = 2 * K - B;
-        const uint64_t nbk = 1ull << B;
-        uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::BUCKETS, (nbk + 2) * 8);
-        bucket_index<L2>(c, E, R, bshift, nbk, bstart);
-        note_bucket_index(c, E, R, bstart, bshift);
-        uint8_t *flags = (uint8_t *)c.ws.get(Workspace::FLAGS, R + 1);
-        uint8_t *in_flag = (uint8_t *)c.ws.get(Workspace::INFLAG, R + 1);
-        if (R) {
-            HIP_CHECK(hipMemsetAsync(in_flag, 0, R, c.stream));
-            first_flag_kernel<L2><<<dim3((unsigned)std::min<uint64_t>(ceil_div(R, 256), 16384)), dim3(256), 0,
-                                    c.stream>>>(E, R, flags);
-            HIP_CHECK(hipGetLastError());
-        }
-        // queries t = to_next(x, 0) of every owned edge, as 4 sorted arrays (one per label of the
-        // querying edge, dist_kernels.hpp: target_split_kernel); every owner's share is a slice of each
-        K2 *qs = (K2 *)c.ws.get(Workspace::QSEND, std::max<uint64_t>(R, 1) * sizeof(K2));
-        std::vector<std::vector<uint64_t>> qoff(4, std::vector<uint64_t>(d.P + 1, 0));
-        std::vector<uint64_t> cstart(5, 0);
-        if (R) {
-            const uint64_t stiles = ceil_div(R, SplitTraits<L2>::TILE);
-            uint32_t *tcnt = (uint32_t *)c.ws.get(Workspace::RTCNT, (4 * stiles + 1) * 4);
-            uint64_t *toff = (uint64_t *)c.ws.get(Workspace::RTOFF, (4 * stiles + 1) * 8);
-            target_split_kernel<L2, true><<<dim3((unsigned)stiles), dim3(256), 0, c.stream>>>(E, R, K, stiles, tcnt,
-                                                                                               nullptr, nullptr);
-            HIP_CHECK(hipGetLastError());
-            uint32_t ep;
-            const uint64_t st = ceil_div(4 * stiles, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(tcnt, 4 * stiles, toff, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-            target_split_kernel<L2, false><<<dim3((unsigned)stiles), dim3(256), 0, c.stream>>>(E, R, K, stiles, nullptr,
-                                                                                                toff, qs);
-            HIP_CHECK(hipGetLastError());
-            uint64_t *g = (uint64_t *)c.ws.get(Workspace::XGATHER, (5 + 4 * (d.P + 1)) * 8);
-            gather_strided_kernel<<<1, 256, 0, c.stream>>>(toff, stiles, 5, g);
-            HIP_CHECK(hipGetLastError());
-            uint64_t *db = (uint64_t *)c.ws.get(Workspace::BOUNDS, (d.P + 1) * 8);
-            HIP_CHECK(hipMemcpyAsync(db, bounds.data(), (d.P + 1) * 8, hipMemcpyHostToDevice, c.stream));
-            class_bounds_kernel<L2><<<dim3((unsigned)ceil_div(4 * (d.P + 1), 256)), dim3(256), 0, c.stream>>>(
-                qs, g, db, (uint32_t)d.P, d.shift2, g + 5);
-            HIP_CHECK(hipGetLastError());
-            std::vector<uint64_t> pos(4 * (d.P + 1));
-            HIP_CHECK(hipMemcpyAsync(cstart.data(), g, 5 * 8, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipMemcpyAsync(pos.data(), g + 5, pos.size() * 8, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));  // bounds / pos are host locals
-            for (int cl = 0; cl < 4; ++cl)
-                for (int j = 0; j <= d.P; ++j) qoff[cl][j] = pos[cl * (d.P + 1) + j] - cstart[cl];
-            // the last owner ends at its class end
-            for (int cl = 0; cl < 4; ++cl) qoff[cl][d.P] = cstart[cl + 1] - cstart[cl];
-        }
-        tr("first flags + split q", R);
-        K2 *qr;
-        uint32_t *unused_c = nullptr;
-        const K2 *qarr[4] = {qs + cstart[0], qs + cstart[1], qs + cstart[2], qs + cstart[3]};
-        const uint64_t nq = exchange_runs<K2>(c, d, 4, qarr, nullptr, qoff, Workspace::QRECV, Workspace::XAC,
-                                         &qr, &unused_c);
-        tr("exchange q", nq);
-        uint8_t *qflag = (uint8_t *)c.ws.get(Workspace::QFLAG, nq + 1);
-        if (nq) {
-            query_join_kernel<L2><<<dim3((unsigned)ceil_div(nq, JoinTraits<L2>::TILE)), dim3(256), 0, c.stream>>>(
-                E, R, bstart, bshift, qr, nq, in_flag, qflag);
-            HIP_CHECK(hipGetLastError());
-        }
-        tr("answer q", nq);
-        // sinks of the missed queries: count + scan now, written once the buffer is sized
-        const uint64_t qtiles = ceil_div(nq, RT_TILE);
-        uint32_t *qtcnt = (uint32_t *)c.ws.get(Workspace::QTCNT, (qtiles + 1) * 4);
-        uint64_t *qtoff = (uint64_t *)c.ws.get(Workspace::QTOFF, (qtiles + 1) * 8);
-        uint64_t nsink = 0;
-        if (nq) {
-            sink_count_kernel<<<dim3((unsigned)qtiles), dim3(RT_BLOCK), 0, c.stream>>>(qflag, nq, qtcnt);
-            HIP_CHECK(hipGetLastError());
-            uint32_t ep;
-            const uint64_t st = ceil_div(qtiles, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(qtcnt, qtiles, qtoff, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-            nsink = read_u64(c, (const unsigned long long *)(qtoff + qtiles));
-        }
-        tr("sink count", nsink);
-        // sources of the owned edges (in_flag is complete: every rank's queries are answered)
-        const uint64_t wtiles = ceil_div(R, DummyTraits<L2>::WTILE);
-        uint32_t *tcnt = (uint32_t *)c.ws.get(Workspace::DTCNT, (wtiles + 1) * 4);
-        uint64_t *toff = (uint64_t *)c.ws.get(Workspace::DTOFF, (wtiles + 1) * 8);
-        uint64_t nsrc = 0;
-        if (R) {
-            dummy_count_kernel<<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(flags, in_flag, R, k_b, tcnt);
-            HIP_CHECK(hipGetLastError());
-            uint32_t ep;
-            const uint64_t st = ceil_div(wtiles, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(tcnt, wtiles, toff, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-            nsrc = read_u64(c, (const unsigned long long *)(toff + wtiles));
-        }
-        K3 *src = (K3 *)c.ws.get(Workspace::DSRC, std::max<uint64_t>(nsrc, 1) * sizeof(K3));
-        if (nsrc) {
-            dummy_write_kernel<L2, L3><<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(E, flags, in_flag, R, K,
-                                                                                            toff, src);
-            HIP_CHECK(hipGetLastError());
-        }
-        tr("sources", nsrc);
-        K3 *ssend = (K3 *)c.ws.get(Workspace::DSEND, std::max<uint64_t>(nsrc, 1) * sizeof(K3));
-        std::vector<std::vector<uint64_t>> doff(1);
-        doff[0] = route<L3, 1>(c, d, src, nsrc, K, 3 * K - 3 * d.m, 3 * d.m, lifted_bounds(bounds, d.m), ssend);
-        K3 *drecv;
-        const K3 *darr[1] = {ssend};
-        const uint64_t nsrc_in = exchange_runs<K3>(c, d, 1, darr, nullptr, doff, Workspace::DRECV, Workspace::XAC,
-                                              &drecv, &unused_c);
-        const uint64_t Draw = nsink + nsrc_in;
-        tr("route + exchange src", nsrc_in);
-        if (Draw) {
-            K3 *da = (K3 *)c.ws.get(Workspace::DA, Draw * sizeof(K3));
-            K3 *db = (K3 *)c.ws.get(Workspace::DB, Draw * sizeof(K3));
-            if (nsink) {
-                sink_write_kernel<L2, L3><<<dim3((unsigned)qtiles), dim3(RT_BLOCK), 0, c.stream>>>(qr, qflag, nq, K,
-                                                                                                  qtoff, da);
-                HIP_CHECK(hipGetLastError());
-            }
-            if (nsrc_in)
-                HIP_CHECK(hipMemcpyAsync(da + nsink, drecv, nsrc_in * sizeof(K3), hipMemcpyDeviceToDevice,
-                                         c.stream));
-            tr("sink write", Draw);
-            D = sort_unique_dummies<L3>(c, K, da, db, Draw, &dk);
-            tr("dummy sort", D);
-        }
-    }
+    const uint64_t D = stage_dummies_dist<L2, L3>(c, d, K, E, R, bounds, tr, &dk);
     T.n_dummy = D + (d.me == 0 ? 1 : 0);
     debug_check_sorted(c, "dummy k-mers (owned)", dk, D);
     const int ev_dummy = tm.mark();
@@ -3245,21 +2954,9 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
     check_error_word(c);
     HIP_CHECK(hipStreamSynchronize(c.stream));
 
-    T.n_rows = out->n;
-    T.extract_ms = tm.ms(ev_start, ev_extract);
-    T.sort_ms = tm.ms(ev_extract, ev_sort);
-    T.unique_ms = tm.ms(ev_sort, ev_unique);
-    T.rc_ms = tm.ms(ev_unique, ev_rc);
-    T.dummy_ms = tm.ms(ev_rc, ev_dummy);
-    T.merge_ms = tm.ms(ev_dummy, ev_merge);
-    T.emit_ms = tm.ms(ev_merge, ev_emit);
-    T.total_ms = tm.ms(ev_start, ev_emit);
+    fill_timings(c, tm, {ev_start, ev_extract, ev_sort, ev_unique, ev_rc, ev_dummy, ev_merge, ev_emit}, out->n);
     for (auto &p : d.xev) T.exchange_ms += tm.ms(p.first, p.second);
     T.sent_bytes = comm.sent_bytes - sent0;
-    T.radix_launches = c.build.radix_launches;
-    T.radix_pass_ms = c.build.radix_launches ? c.build.radix_ms / c.build.radix_launches : 0;
-    T.radix_bytes = c.build.radix_launches ? c.build.radix_bytes / c.build.radix_launches : 0;
-    T.peak_bytes = c.ws.held();
 }
 
 // ------------------------------------------------------------- spilled build (out of HBM, f3)
@@ -3385,8 +3082,7 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
     using K2 = Key<L2>;
     using K3 = Key<L3>;
     const unsigned K = k + 1;
-    const unsigned cbits = bits <= 8 ? 8 : bits <= 16 ? 16 : 32;
-    const uint32_t cmax = cbits == 8 ? 0xFFu : cbits == 16 ? 0xFFFFu : 0xFFFFFFFFu;
+    const uint32_t cmax = count_widths(bits).cmax;
     mtg_boss_timings &T = c.timings;
     EventTimer tm(c.stream);
     const int ev_start = tm.mark();
@@ -3437,13 +3133,7 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
             range_tile_counts_kernel<<<dim3((unsigned)ceil_div(tiles, 4)), dim3(256), 0, c.stream>>>(tbins, tiles, sel,
                                                                                                      tcnt);
             HIP_CHECK(hipGetLastError());
-            uint32_t ep;
-            const uint64_t sct = ceil_div(tiles, 4096);
-            uint64_t *desc = acquire_desc(c, sct, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)sct), dim3(512), 0, c.stream>>>(tcnt, tiles, toff, desc, ep,
-                                                                               &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
+            scan_counts(c, tcnt, tiles, toff);
             range_write_kernel<L2, COUNTED><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(
                 in.seq, in.seq_len, K, both, in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, sel, toff, ka,
                 ca);
@@ -3461,37 +3151,10 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
         // the queries of the range's edges, 4 sorted arrays, sliced by target range
         qcs[j].assign(5, 0);
         qpos[j].assign(4 * (P + 1), 0);
-        K2 *qs = (K2 *)c.ws.get(Workspace::QSEND, std::max<uint64_t>(U, 1) * sizeof(K2));
-        if (U) {
-            const uint64_t stiles = ceil_div(U, SplitTraits<L2>::TILE);
-            uint32_t *qtc = (uint32_t *)c.ws.get(Workspace::RTCNT, (4 * stiles + 1) * 4);
-            uint64_t *qto = (uint64_t *)c.ws.get(Workspace::RTOFF, (4 * stiles + 1) * 8);
-            target_split_kernel<L2, true><<<dim3((unsigned)stiles), dim3(256), 0, c.stream>>>(ka, U, K, stiles, qtc,
-                                                                                               nullptr, nullptr);
-            HIP_CHECK(hipGetLastError());
-            uint32_t ep;
-            const uint64_t sct = ceil_div(4 * stiles, 4096);
-            uint64_t *desc = acquire_desc(c, sct, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)sct), dim3(512), 0, c.stream>>>(qtc, 4 * stiles, qto, desc, ep,
-                                                                               &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-            target_split_kernel<L2, false><<<dim3((unsigned)stiles), dim3(256), 0, c.stream>>>(ka, U, K, stiles, nullptr,
-                                                                                                qto, qs);
-            HIP_CHECK(hipGetLastError());
-            uint64_t *g = (uint64_t *)c.ws.get(Workspace::XGATHER, (5 + 4 * (P + 1)) * 8);
-            gather_strided_kernel<<<1, 256, 0, c.stream>>>(qto, stiles, 5, g);
-            HIP_CHECK(hipGetLastError());
-            uint64_t *db = (uint64_t *)c.ws.get(Workspace::BOUNDS, (P + 1) * 8);
-            HIP_CHECK(hipMemcpyAsync(db, bounds.data(), (P + 1) * 8, hipMemcpyHostToDevice, c.stream));
-            class_bounds_kernel<L2><<<dim3((unsigned)ceil_div(4 * (P + 1), 256)), dim3(256), 0, c.stream>>>(
-                qs, g, db, P, d.shift2, g + 5);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(qcs[j].data(), g, 5 * 8, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipMemcpyAsync(qpos[j].data(), g + 5, qpos[j].size() * 8, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));
+        K2 *qs = split_queries<L2>(c, ka, U, K, P, bounds, d.shift2, qcs[j].data(), qpos[j].data());
+        // absolute positions; the last range ends at its class end
+        if (U)
             for (int cl = 0; cl < 4; ++cl) qpos[j][cl * (P + 1) + P] = qcs[j][cl + 1];
-        }
         qid[j] = st.put(qs, U * sizeof(K2), c.stream);
     }
     T.n_extracted = total / (canonical ? 2 : 1);
@@ -3508,10 +3171,7 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
         const uint64_t Rr = rn[r];
         K2 *E = (K2 *)c.ws.get(Workspace::REAL, std::max<uint64_t>(Rr, 1) * sizeof(K2));
         st.get(eid[r], 0, Rr * sizeof(K2), E, c.stream);
-        const unsigned B = bucket_bits<L2>(Rr, 2 * K);
-        const unsigned bshift = 2 * K - B;
-        uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::BUCKETS, ((1ull << B) + 2) * 8);
-        bucket_index<L2>(c, E, Rr, bshift, 1ull << B, bstart);
+        const BucketIndex bi = real_bucket_index<L2>(c, E, Rr, K, false);
         // every range's queries that target r: 4 sorted runs per range, in class order
         uint64_t nq = 0;
         for (uint32_t j = 0; j < P; ++j)
@@ -3526,67 +3186,19 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
             }
         uint8_t *flags = (uint8_t *)c.ws.get(Workspace::FLAGS, Rr + 1);
         uint8_t *in_flag = (uint8_t *)c.ws.get(Workspace::INFLAG, Rr + 1);
-        uint8_t *qflag = (uint8_t *)c.ws.get(Workspace::QFLAG, nq + 1);
-        if (Rr) {
-            HIP_CHECK(hipMemsetAsync(in_flag, 0, Rr, c.stream));
-            first_flag_kernel<L2><<<dim3((unsigned)std::min<uint64_t>(ceil_div(Rr, 256), 16384)), dim3(256), 0,
-                                    c.stream>>>(E, Rr, flags);
-            HIP_CHECK(hipGetLastError());
-        }
-        if (nq) {
-            query_join_kernel<L2><<<dim3((unsigned)ceil_div(nq, JoinTraits<L2>::TILE)), dim3(256), 0, c.stream>>>(
-                E, Rr, bstart, bshift, qr, nq, in_flag, qflag);
-            HIP_CHECK(hipGetLastError());
-        }
+        first_flags<L2>(c, E, Rr, flags, in_flag);
         // the sinks of r: the queries that missed
-        const uint64_t qtiles = ceil_div(nq, RT_TILE);
-        uint32_t *qtcnt = (uint32_t *)c.ws.get(Workspace::QTCNT, (qtiles + 1) * 4);
-        uint64_t *qtoff = (uint64_t *)c.ws.get(Workspace::QTOFF, (qtiles + 1) * 8);
-        uint64_t nsink = 0;
+        const SinkJoin sj = answer_queries<L2>(c, E, Rr, bi, qr, nq, in_flag);
         K3 *sk = nullptr;
         if (nq) {
-            sink_count_kernel<<<dim3((unsigned)qtiles), dim3(RT_BLOCK), 0, c.stream>>>(qflag, nq, qtcnt);
-            HIP_CHECK(hipGetLastError());
-            uint32_t ep;
-            const uint64_t sct = ceil_div(qtiles, 4096);
-            uint64_t *desc = acquire_desc(c, sct, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)sct), dim3(512), 0, c.stream>>>(qtcnt, qtiles, qtoff, desc, ep,
-                                                                               &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-            nsink = read_u64(c, (const unsigned long long *)(qtoff + qtiles));
-            sk = (K3 *)c.ws.get(Workspace::DA, std::max<uint64_t>(nsink, 1) * sizeof(K3));
-            if (nsink) {
-                sink_write_kernel<L2, L3><<<dim3((unsigned)qtiles), dim3(RT_BLOCK), 0, c.stream>>>(qr, qflag, nq, K,
-                                                                                                  qtoff, sk);
-                HIP_CHECK(hipGetLastError());
-            }
+            sk = (K3 *)c.ws.get(Workspace::DA, std::max<uint64_t>(sj.nsink, 1) * sizeof(K3));
+            if (sj.nsink) write_sinks<L2, L3>(c, K, qr, nq, sj, sk);
         }
-        nsk[r] = nsink;
-        skid[r] = st.put(sk, nsink * sizeof(K3), c.stream);
+        nsk[r] = sj.nsink;
+        skid[r] = st.put(sk, sj.nsink * sizeof(K3), c.stream);
         // the sources of r's nodes (first edges no query hit), every level, routed by lifted prefix
-        const uint64_t wtiles = ceil_div(Rr, DummyTraits<L2>::WTILE);
-        uint32_t *wc = (uint32_t *)c.ws.get(Workspace::DTCNT, (std::max(wtiles, tiles) + 1) * 4);
-        uint64_t *wo = (uint64_t *)c.ws.get(Workspace::DTOFF, (std::max(wtiles, tiles) + 1) * 8);
         uint64_t nsrc = 0;
-        if (Rr) {
-            dummy_count_kernel<<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(flags, in_flag, Rr, k, wc);
-            HIP_CHECK(hipGetLastError());
-            uint32_t ep;
-            const uint64_t sct = ceil_div(wtiles, 4096);
-            uint64_t *desc = acquire_desc(c, sct, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)sct), dim3(512), 0, c.stream>>>(wc, wtiles, wo, desc, ep,
-                                                                               &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-            nsrc = read_u64(c, (const unsigned long long *)(wo + wtiles));
-        }
-        K3 *src = (K3 *)c.ws.get(Workspace::DSRC, std::max<uint64_t>(nsrc, 1) * sizeof(K3));
-        if (nsrc) {
-            dummy_write_kernel<L2, L3><<<dim3((unsigned)wtiles), dim3(256), 0, c.stream>>>(E, flags, in_flag, Rr, K, wo,
-                                                                                            src);
-            HIP_CHECK(hipGetLastError());
-        }
+        K3 *src = write_sources<L2, L3>(c, E, flags, in_flag, Rr, K, k, &nsrc);
         K3 *ssend = (K3 *)c.ws.get(Workspace::DSEND, std::max<uint64_t>(nsrc, 1) * sizeof(K3));
         soffs[r] = route<L3, 1>(c, d, src, nsrc, K, 3 * K - 3 * RB_CHARS, 3 * RB_CHARS, b3, ssend);
         srcid[r] = st.put(ssend, nsrc * sizeof(K3), c.stream);
@@ -3675,9 +3287,7 @@ static void run_suffix(Ctx &c, unsigned k, bool both, unsigned bits, const Suffi
     using K3 = Key<L3>;
     using T = SuffixTraits;
     const unsigned K = k + 1;
-    const unsigned cbits = bits <= 8 ? 8 : bits <= 16 ? 16 : 32;
-    const uint32_t cmax = cbits == 8 ? 0xFFu : cbits == 16 ? 0xFFFFu : 0xFFFFFFFFu;
-    const uint32_t wmax = bits >= 32 ? 0xFFFFFFFFu : (uint32_t)((1ull << bits) - 1);
+    const uint32_t cmax = count_widths(bits).cmax, wmax = count_widths(bits).wmax;
     mtg_boss_timings &Tm = c.timings;
     Tm = mtg_boss_timings{};
     Tm.world = 1;
@@ -3694,16 +3304,7 @@ static void run_suffix(Ctx &c, unsigned k, bool both, unsigned bits, const Suffi
         in.seq, in.seq_len, K, both ? 1 : 0, suf, in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, tcnt,
         nullptr, nullptr, nullptr);
     HIP_CHECK(hipGetLastError());
-    {
-        uint32_t ep;
-        const uint64_t st = ceil_div(tiles, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(tcnt, tiles, toff, desc, ep,
-                                                                          &c.small->counter, &c.small->error);
-        HIP_CHECK(hipGetLastError());
-    }
-    uint64_t N = read_u64(c, (const unsigned long long *)(toff + tiles));
+    uint64_t N = scan_counts_total(c, tcnt, tiles, toff);
     Tm.n_positions = in.seq_len;
     const uint64_t cap = N + (all_sentinel ? 1 : 0);
     K3 *ka = (K3 *)c.ws.get(Workspace::KA, std::max<uint64_t>(cap, 1) * sizeof(K3));

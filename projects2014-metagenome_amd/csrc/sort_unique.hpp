@@ -7,6 +7,23 @@
 
 namespace mtg {
 
+// starts[0..n] = exclusive scan of counts[0..n) (msd_sort.hpp: scan_counts_kernel, one look-back launch)
+static void scan_counts(Ctx &c, const uint32_t *counts, uint64_t n, uint64_t *starts) {
+    uint32_t ep;
+    const uint64_t st = ceil_div(n, 4096);
+    uint64_t *desc = acquire_desc(c, st, &ep);
+    HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
+    scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(counts, n, starts, desc, ep,
+                                                                      &c.small->counter, &c.small->error);
+    HIP_CHECK(hipGetLastError());
+}
+
+// the same, then the total read back (a host sync)
+static uint64_t scan_counts_total(Ctx &c, const uint32_t *counts, uint64_t n, uint64_t *starts) {
+    scan_counts(c, counts, n, starts);
+    return read_u64(c, (const unsigned long long *)(starts + n));
+}
+
 // bucket index of a sorted key array (boss_kernels.hpp: bucket_index_kernel + the grid-wide fill of
 // its long empty runs)
 constexpr uint32_t kBucketRuns = 4096;
@@ -417,16 +434,7 @@ static uint64_t spec_final_level(Ctx &c, Key<L> **keys, uint32_t **vals, uint64_
                                                                                         blo, bhi);
         HIP_CHECK(hipGetLastError());
         uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::MSD_BSTART, (nb + 1) * 8);
-        {
-            uint32_t ep;
-            const uint64_t st = ceil_div(nb, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(cap, nb, bstart, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-        }
-        const uint64_t C = read_u64(c, (const unsigned long long *)(bstart + nb));
+        const uint64_t C = scan_counts_total(c, cap, nb, bstart);
         if (spare && C * sizeof(Key<L>) > rq.spec_into_bytes) spare = nullptr;
         if (!spare) {  // the capacity is known now: both slack-sized buffers (one: fused rc merge, in place) must fit
             const uint64_t fr = c.ws.free_bytes();
@@ -477,15 +485,7 @@ static uint64_t spec_final_level(Ctx &c, Key<L> **keys, uint32_t **vals, uint64_
             spec_counts_kernel<<<dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, c.stream>>>(bstart, cur, nb, cnt);
             HIP_CHECK(hipGetLastError());
             uint64_t *gbase = (uint64_t *)c.ws.get(Workspace::MSD_USTART, (nb + 1) * 8);
-            {
-                uint32_t ep;
-                const uint64_t st = ceil_div(nb, 4096);
-                uint64_t *desc = acquire_desc(c, st, &ep);
-                HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-                scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(cnt, nb, gbase, desc, ep,
-                                                                                  &c.small->counter, &c.small->error);
-                HIP_CHECK(hipGetLastError());
-            }
+            scan_counts(c, cnt, nb, gbase);
             constexpr int CAP = MergeLocalTraits<L>::CAP;
             uint32_t *olist = (uint32_t *)c.ws.get(Workspace::MSD_OVF, nb * 4);  // the overflowing groups
             HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
@@ -601,15 +601,7 @@ static uint64_t spec_final_level(Ctx &c, Key<L> **keys, uint32_t **vals, uint64_
             return ~0ull;
         }
         uint64_t *ustart = (uint64_t *)c.ws.get(Workspace::MSD_USTART, (nb + 1) * 8);
-        {
-            uint32_t ep;
-            const uint64_t st = ceil_div(nb, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(ucount, nb, ustart, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-        }
+        scan_counts(c, ucount, nb, ustart);
         if (!COUNTED && rq.defer_gather && c.knobs.defer_gather && rq.want_gidx) {
             // the fused rc merge follows: leave the distinct keys in their buckets (rq.gap); the
             // compact index of bucket g is ustart[g] (one bucket per group)
@@ -701,16 +693,7 @@ static bool spec_mid_level(Ctx &c, Key<L> **keys, Key<L> **alt, uint64_t n, unsi
                                                                                         bhi, (uint32_t)TILE);
         HIP_CHECK(hipGetLastError());
         uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::MSD_BSTART, (nb + 1) * 8);
-        {
-            uint32_t ep;
-            const uint64_t st = ceil_div(nb, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(cap, nb, bstart, desc, ep,
-                                                                              &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-        }
-        const uint64_t C = read_u64(c, (const unsigned long long *)(bstart + nb));
+        const uint64_t C = scan_counts_total(c, cap, nb, bstart);
         if (C * sizeof(Key<L>) > mid_bytes) {
             if (c.knobs.debug) fprintf(stderr, "[mtg debug] speculative middle level: capacity %lu does not fit\n", (unsigned long)C);
             return false;
@@ -803,13 +786,7 @@ static uint64_t msd_sort_unique(Ctx &c, Key<L> **keys, Key<L> **alt, uint32_t **
             cnt = h;
         }
         bstart = (uint64_t *)c.ws.get(Workspace::MSD_BSTART, (nbuckets + 1) * 8);
-        uint32_t ep;
-        const uint64_t st = ceil_div(nbuckets, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(cnt, nbuckets, bstart, desc, ep,
-                                                                      &c.small->counter, &c.small->error);
-        HIP_CHECK(hipGetLastError());
+        scan_counts(c, cnt, nbuckets, bstart);
         if (lev == 1 && level1_done) {
             b = bb;
             return;
@@ -928,15 +905,7 @@ static uint64_t msd_sort_unique(Ctx &c, Key<L> **keys, Key<L> **alt, uint32_t **
                 gsize, nbuckets, G, gf);
             HIP_CHECK(hipGetLastError());
             uint64_t *gpos = (uint64_t *)c.ws.get(Workspace::MSD_USTART, (nbuckets + 1) * 8);
-            uint32_t ep;
-            const uint64_t st = ceil_div(nbuckets, 4096);
-            uint64_t *desc = acquire_desc(c, st, &ep);
-            HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-            scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(gf, nbuckets, gpos, desc, ep,
-                                                                          &c.small->counter, &c.small->error);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(&ngroups, gpos + nbuckets, 8, hipMemcpyDeviceToHost, c.stream));
-            HIP_CHECK(hipStreamSynchronize(c.stream));
+            ngroups = scan_counts_total(c, gf, nbuckets, gpos);
             gstart = (uint64_t *)c.ws.get(Workspace::MSD_GSTART, (ngroups + 1) * 8);
             // each group's bucket range: the fused rc merge's canonical ranges, or the output's bucket index
             uint64_t *gbucket = b <= 32 ? (uint64_t *)c.ws.get(Workspace::MSD_GBUCKET, (ngroups + 1) * 8) : nullptr;
@@ -1120,13 +1089,7 @@ static uint64_t msd_sort_unique(Ctx &c, Key<L> **keys, Key<L> **alt, uint32_t **
         }
         // pack: ustart = exclusive scan of ucount, gather tmp (= *alt) -> *keys
         uint64_t *ustart = (uint64_t *)c.ws.get(Workspace::MSD_USTART, (ngroups + 1) * 8);
-        uint32_t ep;
-        const uint64_t st = ceil_div(ngroups, 4096);
-        uint64_t *desc = acquire_desc(c, st, &ep);
-        HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
-        scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(ucount, ngroups, ustart, desc, ep,
-                                                                      &c.small->counter, &c.small->error);
-        HIP_CHECK(hipGetLastError());
+        scan_counts(c, ucount, ngroups, ustart);
         // the output's bucket index over the top b bits comes out of the gather (the fused rc merge
         // of the canonical keys reuses it instead of a bucket_index pass: 0.44 ms at configs[1])
         // (only for the sorts the fused rc merge follows: rq.want_gidx)

@@ -124,6 +124,15 @@ def test_dist_collect_modes(monkeypatch, env):
         check_dist(k, reads, P, canonical, bits)
 
 
+@pytest.mark.parametrize("k", [45, 70])
+def test_dist_query_sinks_multiword_keys(monkeypatch, k):
+    # the queried sink join with two-word (k = 45) and four-word (k = 70) real keys: the query splitter and
+    # answerer it shares with the spilled build, which the one-word cases above do not instantiate
+    monkeypatch.setenv("MTG_DIST_SINKS", "query")
+    reads = _random_reads(100 + k, 400, 150, 4000, n_rate=0.01, lower=True)
+    check_dist(k, reads, 3, canonical=k == 45, bits=8)
+
+
 def test_dist_empty_and_lopsided_ranks():
     reads = _random_reads(5, 300, 150, 3000)
     for P in (2, 5, 8):
