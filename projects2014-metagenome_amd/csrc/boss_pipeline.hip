@@ -41,6 +41,7 @@
 #include "radix_sort.hpp"
 #include "ctx.hpp"
 #include "sort_unique.hpp"
+#include "collect_stage.hpp"
 #include "dummy_stage.hpp"
 
 namespace mtg {
@@ -48,15 +49,6 @@ namespace mtg {
 static thread_local std::string g_last_error;
 
 static void set_error(const std::string &msg) { g_last_error = msg; }
-
-struct BuildInput {
-    const uint8_t *seq;
-    uint64_t seq_len;
-    const uint64_t *read_starts;
-    const uint32_t *read_counts;
-    uint64_t n_reads;
-    const uint64_t *rid_at = nullptr;  // per-read counts: the read of every 4 K-position block
-};
 
 struct BuildOutput {
     uint8_t *W;
@@ -77,7 +69,7 @@ template <int L2, bool COUNTED>
 static uint64_t stage_extract(Ctx &c, unsigned K, bool canonical, uint32_t cmax, const BuildInput &in,
                               Key<L2> **ka, Key<L2> **kb, uint32_t **ca, uint32_t **cb) {
     using K2 = Key<L2>;
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+    const uint64_t npos = n_windows(in, K);
     c.timings.n_positions = npos;
     *ka = (K2 *)c.ws.get(Workspace::KA, npos * sizeof(K2));
     *kb = (K2 *)c.ws.get(Workspace::KB, npos * sizeof(K2));
@@ -140,7 +132,7 @@ static bool stage_extract_windows(Ctx &c, unsigned K, bool canonical, uint32_t c
     HIP_CHECK(hipStreamSynchronize(c.stream));
     if (bad) return false;
     if (c.knobs.debug) fprintf(stderr, "[mtg debug] one-window reads: %lu reads -> %llu k-mers\n", (unsigned long)n, N);
-    c.timings.n_positions = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+    c.timings.n_positions = n_windows(in, K);
     c.timings.n_extracted = N;
     *N_out = N;
     return true;
@@ -158,12 +150,7 @@ static MsdPlan fused_plan(const Ctx &c, uint64_t N, unsigned nbits, double dup, 
     unsigned b1 = 0;
     if (c.knobs.fused_b1) b1 = std::min(c.knobs.fused_b1, T);
     else if (c.knobs.wide_b1 && p.levels == 3 && !c.knobs.min_levels && T <= 10 + MSD_DBITS) b1 = 10;
-    if (!b1) return p;
-    MsdPlan q{};
-    q.levels = 1 + (T - b1 + MSD_DBITS - 1) / MSD_DBITS;
-    q.digit_end[1] = b1;
-    for (unsigned l = 2; l <= q.levels; ++l) q.digit_end[l] = b1 + (T - b1) * (l - 1) / (q.levels - 1);
-    return q;
+    return b1 ? level1_fixed_plan(b1, T) : p;
 }
 
 // K1 fused with K2's first partition level (extract_partition.hpp), for 2-bit u64 keys on
@@ -215,7 +202,7 @@ static void fused_pass_a(Ctx &c, unsigned K, bool canonical, const BuildInput &i
                          int fbk = 512) {
     // fbk: pass B's workgroup size (fused_block<L>: 512 for u64 keys, 256 for u128); K > 32: the wide
     // histogram kernel (u128 windows)
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+    const uint64_t npos = n_windows(in, K);
     constexpr uint32_t M = 1u << 19, SLOTS = 1u << 21;
     unsigned long long *table = (unsigned long long *)c.ws.get(Workspace::DUP_TABLE, (SLOTS + 2) * 8ull);
     HIP_CHECK(hipMemsetAsync(table, 0, (SLOTS + 2) * 8ull, c.stream));
@@ -512,7 +499,7 @@ static bool stage_extract_fused(Ctx &c, unsigned K, bool canonical, uint32_t cma
     if constexpr (L2 != 1) {
         return false;
     } else {
-        const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+        const uint64_t npos = n_windows(in, K);
         if (!fused_applies(c, K, npos)) return false;
         FusedA A;
         // the speculative level-1 layout: uncounted single builds big enough that a sample sizes the
@@ -625,16 +612,11 @@ static std::vector<uint64_t> balanced_bounds(const uint64_t *hist, uint64_t nb, 
 // (memory_preallocated, else the free HBM plus what the workspace already holds)
 template <int L2, bool COUNTED>
 static uint32_t plan_ranges(Ctx &c, unsigned K, bool canonical, const BuildInput &in) {
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+    const uint64_t npos = n_windows(in, K);
     if (K < RB_CHARS + 1) return 1;  // at most 4^4 distinct k-mers: never worth a range
     if (c.knobs.force_ranges) return c.knobs.force_ranges;
     const double per_key = (double)sizeof(Key<L2>) + (COUNTED ? 4.0 : 0.0);
-    double budget = c.params.mem_budget;
-    if (budget <= 0) {
-        size_t fr = 0, tot = 0;
-        HIP_CHECK(hipMemGetInfo(&fr, &tot));
-        budget = 0.9 * ((double)fr + (double)c.ws.held());
-    }
+    const double budget = hbm_budget(c);
     // single pass: KA + KB over every window, then the real edges, rc and dummy buffers
     if ((double)npos * per_key * 2.5 <= budget && !c.params.disk) return 1;
     const double keys = (double)npos * (canonical ? 2.0 : 1.0);
@@ -647,81 +629,34 @@ template <int L2, bool COUNTED>
 static uint64_t collect_ranges(Ctx &c, unsigned K, bool canonical, uint32_t cmax, const BuildInput &in,
                                uint32_t P, Key<L2> **real, uint32_t **realc) {
     using K2 = Key<L2>;
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
-    c.timings.n_positions = npos;
+    c.timings.n_positions = n_windows(in, K);
     const int both = canonical ? 1 : 0;
-    constexpr int TILE = RangeTraits<L2>::TILE;
-    const uint64_t tiles = ceil_div(npos, TILE);
-    // count pass: per-tile counts of the 4^RB_CHARS top-char bins, and their column sums
-    std::vector<uint64_t> hist(RB_BINS, 0);
-    uint16_t *tbins = (uint16_t *)c.ws.get(Workspace::RANGE_BINS, std::max<uint64_t>(tiles, 1) * RB_BINS * 2);
-    if (tiles) {
-        auto *dh = (unsigned long long *)c.ws.get(Workspace::XHIST, RB_BINS * 8);
-        HIP_CHECK(hipMemsetAsync(dh, 0, RB_BINS * 8, c.stream));
-        range_count_kernel<L2><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, both, tbins);
-        HIP_CHECK(hipGetLastError());
-        range_bins_reduce_kernel<<<dim3((unsigned)std::min<uint64_t>(tiles, 2048)), dim3(RB_BINS), 0, c.stream>>>(
-            tbins, tiles, dh);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(hist.data(), dh, RB_BINS * 8, hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-    }
+    RangeScan<L2> scan(c, in, K, both);
+    std::vector<uint64_t> hist;
+    scan.fetch(c, &hist);
     uint64_t total = 0;
     for (uint64_t v : hist) total += v;
     P = std::min<uint32_t>(P, RB_BINS);
     const std::vector<uint64_t> bounds = balanced_bounds(hist.data(), RB_BINS, (int)P);
     c.timings.n_batches = P;
-    uint64_t off = 0, cap = 0;
-    *real = nullptr;
-    *realc = nullptr;
-    uint32_t *tcnt = (uint32_t *)c.ws.get(Workspace::DTCNT, (tiles + 1) * 4);
-    uint64_t *toff = (uint64_t *)c.ws.get(Workspace::DTOFF, (tiles + 1) * 8);
+    AppendSet<L2, COUNTED> set{c, Workspace::REAL, Workspace::REALC};
+    scan.tile_offsets(c);
     for (uint32_t j = 0; j < P; ++j) {
         const uint32_t lo = (uint32_t)bounds[j], hi = (uint32_t)bounds[j + 1];
         uint64_t nj = 0;
         for (uint32_t b = lo; b < hi; ++b) nj += hist[b];
         if (!nj) continue;
-        K2 *ka = (K2 *)c.ws.get(Workspace::KA, nj * sizeof(K2));
-        K2 *kb = (K2 *)c.ws.get(Workspace::KB, nj * sizeof(K2));
-        uint32_t *ca = COUNTED ? (uint32_t *)c.ws.get(Workspace::CA, nj * 4) : nullptr;
-        uint32_t *cb = COUNTED ? (uint32_t *)c.ws.get(Workspace::CB, nj * 4) : nullptr;
         BinSet sel{};
         sel.add(lo, hi);
-        range_tile_counts_kernel<<<dim3((unsigned)ceil_div(tiles, 4)), dim3(256), 0, c.stream>>>(tbins, tiles, sel,
-                                                                                                 tcnt);
-        HIP_CHECK(hipGetLastError());
-        scan_counts(c, tcnt, tiles, toff);
-        range_write_kernel<L2, COUNTED><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(
-            in.seq, in.seq_len, K, both, in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, sel, toff, ka, ca);
-        HIP_CHECK(hipGetLastError());
-        const uint64_t N = read_u64(c, (const unsigned long long *)(toff + tiles));
-        if (N != nj) throw std::runtime_error("range extraction count differs from its histogram");
-        // the range fills (hi - lo) / RB_BINS of the top-char space: plan the MSD depth as if its
-        // keys were spread over all of it
-        const double spread = (double)RB_BINS / (double)(hi - lo);
-        const double dup = estimate_dup<L2>(c, ka, N, 8.0) / spread;
-        SortRequest<L2> rq;
-        rq.track_partition = j == 0;  // the roofline's partition pass: the first range's first level
-        const uint64_t U = msd_sort_unique<L2, COUNTED>(c, &ka, &kb, &ca, &cb, N, 2 * K, cmax, dup, rq);
-        if (off + U > cap) {
-            // first range: size the real edges from its distinct ratio (+25 %); later growth keeps
-            // what is already appended
-            const uint64_t want = off == 0 ? (uint64_t)((double)U / (double)N * (double)total * 1.25) + U
-                                           : (off + U) + (off + U) / 4;
-            cap = std::max(want, off + U);
-            *real = (K2 *)c.ws.get(Workspace::REAL, cap * sizeof(K2), off * sizeof(K2), c.stream);
-            if (COUNTED) *realc = (uint32_t *)c.ws.get(Workspace::REALC, cap * 4, off * 4, c.stream);
-        }
-        HIP_CHECK(hipMemcpyAsync(*real + off, ka, U * sizeof(K2), hipMemcpyDeviceToDevice, c.stream));
-        if (COUNTED) HIP_CHECK(hipMemcpyAsync(*realc + off, ca, U * 4, hipMemcpyDeviceToDevice, c.stream));
-        off += U;
-    }
-    if (!*real) {
-        *real = (K2 *)c.ws.get(Workspace::REAL, sizeof(K2));
-        if (COUNTED) *realc = (uint32_t *)c.ws.get(Workspace::REALC, 4);
+        K2 *ka, *kb;
+        uint32_t *ca, *cb;
+        // (track: the roofline's partition pass is the first range's first level)
+        const uint64_t U = extract_range_sorted<L2, COUNTED>(c, scan, in, K, both, cmax, sel, nj, j == 0, &ka, &kb, &ca,
+                                                             &cb);
+        set.append(ka, ca, U, total, nj);  // sized from the first range's distinct ratio
     }
     c.timings.n_extracted = total / (canonical ? 2 : 1);  // valid windows (one k-mer per strand each)
-    return off;
+    return set.finish(real, realc);
 }
 
 // ------------------------------------------------ canonical key rounds of the fused K1 (configs[3])
@@ -744,7 +679,7 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     // L = 2: u128 windows (32 < K <= 64, BASELINE configs[2]'s k = 63) -- the wide pass A and the generic
     // pass B on 256-thread tiles; the later levels are the MSD sort's exact ones
     using K2 = Key<L>;
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+    const uint64_t npos = n_windows(in, K);
     if (c.knobs.range_scan || c.params.disk || !fused_applies(c, K, npos, L == 1 ? 32 : 64)) return false;
     // a previous build's stage buffers would crowd out this build's rounds: they go now (and are
     // allocated again at the sizes this build needs)
@@ -758,12 +693,7 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     MsdPlan plan = L == 1 ? fused_plan(c, N, 2 * K, A.dup, !COUNTED && K <= 32) : msd_plan<L>(c, N, 2 * K, A.dup);
     if (L == 2 && plan.levels && plan.digit_end[1] > 9) {
         // the u128 pass B takes at most 9 bits: level 1 of 9, the rest split over the later levels
-        const unsigned T = plan.digit_end[plan.levels];
-        MsdPlan q{};
-        q.levels = 1 + (T - 9 + MSD_DBITS - 1) / MSD_DBITS;
-        q.digit_end[1] = 9;
-        for (unsigned l = 2; l <= q.levels; ++l) q.digit_end[l] = 9 + (T - 9) * (l - 1) / (q.levels - 1);
-        plan = q;
+        plan = level1_fixed_plan(9, plan.digit_end[plan.levels]);
     }
     if (!plan.levels) return false;
     const unsigned b1 = plan.digit_end[1];
@@ -773,12 +703,7 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     // rounds: the later stages hold ~5 keys of 8 B per distinct canonical k-mer (the canonical set, the
     // real edges, the rc sort's two buffers) plus the rows; a round holds its keys twice (+ counts)
     uint32_t R = c.knobs.force_ranges;
-    double budget = c.params.mem_budget;
-    if (budget <= 0) {
-        size_t fr = 0, tot = 0;
-        HIP_CHECK(hipMemGetInfo(&fr, &tot));
-        budget = 0.9 * ((double)fr + (double)c.ws.held());
-    }
+    const double budget = hbm_budget(c);
     const double u_est = std::min((double)N, (double)N / A.dup * 1.25);
     if (!R) {
         const double kb = (double)sizeof(K2);
@@ -873,17 +798,12 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     c.timings.n_extracted = N;
     c.timings.n_batches = R;
     c.timings.collect_mode = 2;
-    uint64_t off = 0, cap = 0;
-    *out = nullptr;
-    *outc = nullptr;
+    AppendSet<L, COUNTED> set{c, Workspace::CANON, Workspace::CANONC};
     bool first = true;
     // the canonical set sized from pass A's duplication estimate up front, so that every round's final
     // gather writes its distinct keys straight into it (SortRequest::out) instead of into the round buffer and a
     // copy after (a 19 GB copy per configs[3] round); a round that finds more falls back to that copy
-    if (R > 1 && !COUNTED) {
-        cap = (uint64_t)u_est + 65536;
-        *out = (K2 *)c.ws.get(Workspace::CANON, cap * sizeof(K2));
-    }
+    if (R > 1 && !COUNTED) set.reserve((uint64_t)u_est + 65536);
     // the rc stage reads the canonical set through a bucket index over the rc sort's final bits (its plan
     // for the set's size, estimated here from pass A's duplication): each round's speculative gather writes
     // its buckets' entries (SortRequest::ridx) instead of a bucket_index pass over the whole set after the rounds
@@ -904,7 +824,7 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
             const uint64_t lo = bb[r] << (fb_est - b1), hi = bb[r + 1] << (fb_est - b1);
             if (lo < hi)
                 fill_u64_kernel<<<dim3((unsigned)std::min<uint64_t>(ceil_div(hi - lo, 256), 4096)), dim3(256), 0, c.stream>>>(
-                    rgi, lo, hi, off);
+                    rgi, lo, hi, set.off);
             HIP_CHECK(hipGetLastError());
         }
         if (!nr[r]) continue;
@@ -940,38 +860,23 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
             const double rho = ((double)n / nbk) / ((double)N / (double)(1ull << T));
             if (rho < 0.75 && T >= bp + 2) rplan.digit_end[plan.levels] = T - 1;
         }
-        if (*out && off < cap && (!COUNTED || *outc)) {
-            rq.out = *out + off, rq.out_cap = cap - off;
-            rq.out_vals = COUNTED ? *outc + off : nullptr;  // (the counts travel with their keys)
+        if (set.room()) {
+            rq.out = set.tail(), rq.out_cap = set.room();
+            rq.out_vals = set.tail_vals();  // (the counts travel with their keys)
         }
-        if (rgi_ok) rq.ridx = RoundIndex{rgi, fb_est, off, bb[r] << (fb_est - b1), bb[r + 1] << (fb_est - b1)};
+        if (rgi_ok) rq.ridx = RoundIndex{rgi, fb_est, set.off, bb[r] << (fb_est - b1), bb[r + 1] << (fb_est - b1)};
         rq.force_plan = &rplan;
         const uint64_t U = msd_sort_unique<L, COUNTED>(c, &xa, &xb, &xac, &xbc, n, 2 * K, cmax, A.dup, rq);
         rgi_ok = rgi_ok && rq.ridx_written;
         first = false;
         tr("rounds: sort", r, U);
-        if (off + U > cap) {
-            // first round: size the canonical set from its distinct ratio (+25 %); later growth keeps
-            // what is already appended
-            const uint64_t want = off == 0 ? (uint64_t)((double)U / (double)n * (double)N * 1.25) + U
-                                           : (off + U) + (off + U) / 4;
-            cap = std::max(want, off + U);
-            *out = (K2 *)c.ws.get(Workspace::CANON, cap * sizeof(K2), off * sizeof(K2), c.stream);
-            if (COUNTED) *outc = (uint32_t *)c.ws.get(Workspace::CANONC, cap * 4, off * 4, c.stream);
-        }
-        if (xa != *out + off) {  // (gathered into the round buffer, not straight into the set)
-            HIP_CHECK(hipMemcpyAsync(*out + off, xa, U * sizeof(K2), hipMemcpyDeviceToDevice, c.stream));
-            if (COUNTED) HIP_CHECK(hipMemcpyAsync(*outc + off, xac, U * 4, hipMemcpyDeviceToDevice, c.stream));
-        }
-        off += U;
+        // (sized from the first round's distinct ratio; no copy where the sort gathered straight into the set)
+        set.append(xa, xac, U, N, n);
         if (c.knobs.debug)
             fprintf(stderr, "[mtg debug]   round %u: buckets [%lu, %lu) n=%lu -> %lu distinct\n", r,
                     (unsigned long)bb[r], (unsigned long)bb[r + 1], (unsigned long)n, (unsigned long)U);
     }
-    if (!*out) {
-        *out = (K2 *)c.ws.get(Workspace::CANON, sizeof(K2));
-        if (COUNTED) *outc = (uint32_t *)c.ws.get(Workspace::CANONC, 4);
-    }
+    const uint64_t off = set.finish(out, outc);
     debug_check_sorted(c, "canonical rounds", *out, off);
     // the round buffers (sized for the largest round) go; the rc stage takes KB and SPEC_A again at
     // its own size
@@ -1495,15 +1400,6 @@ static uint32_t dist_coresident(Ctx &c, Dist &d) {
     return coresident_count(all.data(), d.P, h);
 }
 
-// a rank's HBM budget for planning its rounds: memory_preallocated, else its share of the free HBM
-// (the ranks on its GPU split it) plus what its workspace holds
-static double dist_budget(const Ctx &c, const Dist &d) {
-    if (c.params.mem_budget > 0) return c.params.mem_budget;
-    size_t fr = 0, tot = 0;
-    HIP_CHECK(hipMemGetInfo(&fr, &tot));
-    return 0.9 * ((double)fr / (double)std::max<uint32_t>(d.coresident, 1) + (double)c.ws.held());
-}
-
 // prefix index of a sorted 2-bit array: start[p] = first key with prefix >= p, p in [0, nb]
 template <int L2>
 static uint64_t *prefix_index(Ctx &c, const Dist &d, Workspace::Slot slot, const Key<L2> *keys, uint64_t n) {
@@ -1815,14 +1711,14 @@ static uint64_t stage_dummies_dist(Ctx &c, Dist &d, unsigned K, const Key<L2> *E
 template <int L2, bool COUNTED>
 static uint32_t plan_rounds_dist(Ctx &c, Dist &d, unsigned K, bool canonical, const BuildInput &in) {
     uint64_t want = 1;
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+    const uint64_t npos = n_windows(in, K);
     // bins of RB_CHARS node chars keep every emission group on one rank only for k - 1 >= RB_CHARS
     const bool can = K >= RB_CHARS + 2;
     if (can && c.knobs.force_ranges) {
         want = c.knobs.force_ranges;
     } else if (can) {
         const double per_key = (double)sizeof(Key<L2>) + (COUNTED ? 4.0 : 0.0);
-        const double budget = dist_budget(c, d);
+        const double budget = hbm_budget(c, d.coresident);
         // single pass: KA + KB over every window, the exchange buffers and the owned real edges
         if ((double)npos * per_key * 3.0 > budget || c.params.disk) {
             const double keys = (double)npos * (canonical ? 2.0 : 1.0);
@@ -1850,31 +1746,18 @@ static uint64_t collect_ranges_dist(Ctx &c, Dist &d, unsigned K, bool canonical,
                                     const BuildInput &in, uint32_t rounds, Key<L2> **real, uint32_t **realc,
                                     std::vector<uint64_t> *owner_bounds, Tracer &tr) {
     using K2 = Key<L2>;
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
-    c.timings.n_positions = npos;
+    c.timings.n_positions = n_windows(in, K);
     c.timings.n_batches = rounds;
     const int both = canonical ? 1 : 0;
-    constexpr int TILE = RangeTraits<L2>::TILE;
-    const uint64_t tiles = ceil_div(npos, TILE);
     // count pass over this rank's reads, then the global bin histogram
-    auto *dh = (unsigned long long *)c.ws.get(Workspace::XHIST, RB_BINS * 8);
-    HIP_CHECK(hipMemsetAsync(dh, 0, RB_BINS * 8, c.stream));
-    uint16_t *tbins = (uint16_t *)c.ws.get(Workspace::RANGE_BINS, std::max<uint64_t>(tiles, 1) * RB_BINS * 2);
-    if (tiles) {
-        range_count_kernel<L2><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, both, tbins);
-        HIP_CHECK(hipGetLastError());
-        range_bins_reduce_kernel<<<dim3((unsigned)std::min<uint64_t>(tiles, 2048)), dim3(RB_BINS), 0, c.stream>>>(
-            tbins, tiles, dh);
-        HIP_CHECK(hipGetLastError());
-    }
-    std::vector<uint64_t> local(RB_BINS), glob(RB_BINS);
-    HIP_CHECK(hipMemcpyAsync(local.data(), dh, RB_BINS * 8, hipMemcpyDeviceToHost, c.stream));
+    RangeScan<L2> scan(c, in, K, both);
+    std::vector<uint64_t> local, glob;
+    scan.fetch(c, &local, false);
     const int e0 = d.tm->mark();
-    d.comm.allreduce_sum_u64((uint64_t *)dh, RB_BINS, c.stream);
+    d.comm.allreduce_sum_u64((uint64_t *)scan.hist, RB_BINS, c.stream);
     d.xev.push_back({e0, d.tm->mark()});
-    HIP_CHECK(hipMemcpyAsync(glob.data(), dh, RB_BINS * 8, hipMemcpyDeviceToHost, c.stream));
-    HIP_CHECK(hipStreamSynchronize(c.stream));
-    tr("range count", tiles);
+    scan.fetch(c, &glob);
+    tr("range count", scan.tiles);
     // owner intervals, then each cut into `rounds` batches
     const std::vector<uint64_t> ob = balanced_bounds(glob.data(), RB_BINS, d.P);
     std::vector<std::vector<uint64_t>> bb(d.P);
@@ -1885,38 +1768,20 @@ static uint64_t collect_ranges_dist(Ctx &c, Dist &d, unsigned K, bool canonical,
     *owner_bounds = ob;
     uint64_t own_total = 0;
     for (uint64_t b = ob[d.me]; b < ob[d.me + 1]; ++b) own_total += glob[b];
-    uint32_t *tcnt = (uint32_t *)c.ws.get(Workspace::DTCNT, (tiles + 1) * 4);
-    uint64_t *toff = (uint64_t *)c.ws.get(Workspace::DTOFF, (tiles + 1) * 8);
-    uint64_t off = 0, cap = 0, extracted = 0;
-    *real = nullptr;
-    *realc = nullptr;
+    scan.tile_offsets(c);
+    AppendSet<L2, COUNTED> set{c, Workspace::REAL, Workspace::REALC};
+    uint64_t extracted = 0;
     for (uint32_t r = 0; r < rounds; ++r) {
         BinSet sel{};
         for (int o = 0; o < d.P; ++o) sel.add((uint32_t)bb[o][r], (uint32_t)bb[o][r + 1]);
         uint64_t nj = 0;
         for (uint32_t b = 0; b < RB_BINS; ++b)
             if (sel.has(b)) nj += local[b];
-        K2 *ka = (K2 *)c.ws.get(Workspace::KA, std::max<uint64_t>(nj, 1) * sizeof(K2));
-        K2 *kb = (K2 *)c.ws.get(Workspace::KB, std::max<uint64_t>(nj, 1) * sizeof(K2));
-        uint32_t *ca = COUNTED ? (uint32_t *)c.ws.get(Workspace::CA, std::max<uint64_t>(nj, 1) * 4) : nullptr;
-        uint32_t *cb = COUNTED ? (uint32_t *)c.ws.get(Workspace::CB, std::max<uint64_t>(nj, 1) * 4) : nullptr;
-        uint64_t Ul = 0;
-        if (nj) {
-            range_tile_counts_kernel<<<dim3((unsigned)ceil_div(tiles, 4)), dim3(256), 0, c.stream>>>(tbins, tiles, sel,
-                                                                                                     tcnt);
-            HIP_CHECK(hipGetLastError());
-            scan_counts(c, tcnt, tiles, toff);
-            range_write_kernel<L2, COUNTED><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(
-                in.seq, in.seq_len, K, both, in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, sel, toff, ka, ca);
-            HIP_CHECK(hipGetLastError());
-            const uint64_t N = read_u64(c, (const unsigned long long *)(toff + tiles));
-            if (N != nj) throw std::runtime_error("range extraction count differs from its histogram");
-            const double spread = (double)RB_BINS / (double)std::max<uint32_t>(1, sel.size());
-            const double dup = estimate_dup<L2>(c, ka, N, 8.0) / spread;
-            SortRequest<L2> rq;
-            rq.track_partition = r == 0;  // the roofline's partition pass: the first round's first level
-            Ul = msd_sort_unique<L2, COUNTED>(c, &ka, &kb, &ca, &cb, N, 2 * K, cmax, dup, rq);
-        }
+        K2 *ka, *kb;
+        uint32_t *ca, *cb;
+        // (track: the roofline's partition pass is the first round's first level)
+        const uint64_t Ul = extract_range_sorted<L2, COUNTED>(c, scan, in, K, both, cmax, sel, nj, r == 0, &ka, &kb,
+                                                              &ca, &cb);
         extracted += nj;
         tr("round collect", nj, Ul);
         // every owner's slice of the sorted local keys: the bin index of the keys at the owner bounds
@@ -1950,28 +1815,13 @@ static uint64_t collect_ranges_dist(Ctx &c, Dist &d, unsigned K, bool canonical,
             }
             tr("round exchange + merge", n1, U);
         }
-        if (off + U > cap) {
-            // first filled round: size the owned real edges from its share of the owner's range
-            uint64_t gr = 0;
-            for (uint64_t b = bb[d.me][r]; b < bb[d.me][r + 1]; ++b) gr += glob[b];
-            const uint64_t want = off == 0 && gr ? (uint64_t)((double)U / (double)gr * (double)own_total * 1.25) + U
-                                                 : (off + U) + (off + U) / 4;
-            cap = std::max(want, off + U);
-            *real = (K2 *)c.ws.get(Workspace::REAL, cap * sizeof(K2), off * sizeof(K2), c.stream);
-            if (COUNTED) *realc = (uint32_t *)c.ws.get(Workspace::REALC, cap * 4, off * 4, c.stream);
-        }
-        if (U) {
-            HIP_CHECK(hipMemcpyAsync(*real + off, xa, U * sizeof(K2), hipMemcpyDeviceToDevice, c.stream));
-            if (COUNTED) HIP_CHECK(hipMemcpyAsync(*realc + off, xac, U * 4, hipMemcpyDeviceToDevice, c.stream));
-        }
-        off += U;
-    }
-    if (!*real) {
-        *real = (K2 *)c.ws.get(Workspace::REAL, sizeof(K2));
-        if (COUNTED) *realc = (uint32_t *)c.ws.get(Workspace::REALC, 4);
+        // first filled round: the owned real edges sized from its share of the owner's range
+        uint64_t gr = 0;
+        for (uint64_t b = bb[d.me][r]; b < bb[d.me][r + 1]; ++b) gr += glob[b];
+        set.append(xa, xac, U, own_total, gr);
     }
     c.timings.n_extracted = extracted / (canonical ? 2 : 1);  // valid windows (one k-mer per strand each)
-    return off;
+    return set.finish(real, realc);
 }
 
 // ------------------------------------------ multi-GPU: the extraction routed straight to the owners
@@ -2022,7 +1872,6 @@ static uint64_t routed_pieces(Ctx &c, Dist &d, unsigned K, uint32_t cmax, const 
                               const std::vector<uint64_t> &H, uint32_t Q, Key<1> **out, uint32_t **outc,
                               double *xspan_ms, double *hidden_ms, Tracer &tr) {
     using K2 = Key<1>;
-    constexpr uint32_t NBH = 1u << FUSED_HB;
     const int P = d.P;
     std::vector<std::vector<uint64_t>> sub(P);
     for (int o = 0; o < P; ++o) {
@@ -2099,16 +1948,8 @@ static uint64_t routed_pieces(Ctx &c, Dist &d, unsigned K, uint32_t cmax, const 
     for (uint32_t q = 0; q < Q; ++q) {
         HIP_CHECK(hipStreamWaitEvent(c.stream, ev_x[q], 0));
         const uint64_t rb0 = sub[d.me][q], rb1 = sub[d.me][q + 1];
-        uint64_t nown = 0;
-        for (uint32_t i = 0; i < NBH; ++i) {
-            const uint32_t b = i >> (FUSED_HB - B1);
-            if (b >= rb0 && b < rb1) {
-                hown[q][b] += (uint32_t)H[i];
-                nown += H[i];
-            }
-        }
         const uint64_t nq = pbase[q + 1] - pbase[q];
-        if (nown != nq) throw std::runtime_error("received k-mers differ from the global histogram of the owned piece");
+        owner_level1(H, B1, rb0, rb1, hown[q], nq, "received k-mers differ from the global histogram of the owned piece");
         uint64_t Ur = 0;
         K2 *pa = xa + pbase[q], *pb = xb + pbase[q];
         uint32_t *pac = COUNTED ? xac + pbase[q] : nullptr, *pbc = COUNTED ? xbc + pbase[q] : nullptr;
@@ -2117,18 +1958,8 @@ static uint64_t routed_pieces(Ctx &c, Dist &d, unsigned K, uint32_t cmax, const 
             const double spread = (double)nb1 / (double)std::max<uint64_t>(1, rb1 - rb0);
             if (dup_raw == 0) dup_raw = estimate_dup<1>(c, pa, nq, 8.0);
             const double dup = dup_raw / spread;
-            MsdPlan plan = msd_plan<1>(c, nq, 2 * K, dup);
-            unsigned T = plan.levels ? plan.digit_end[plan.levels] : 0;
-            T = std::min(2 * K, std::max(T, B1 + 1));
-            MsdPlan fp{};
-            fp.levels = 1 + (T - B1 + MSD_DBITS - 1) / MSD_DBITS;
-            fp.digit_end[1] = B1;
-            for (unsigned l = 2; l <= fp.levels; ++l) fp.digit_end[l] = B1 + (T - B1) * (l - 1) / (fp.levels - 1);
-            SortRequest<1> rq;
-            rq.hist1 = dh1;
-            rq.level1_done = true;
-            rq.force_plan = &fp;
-            rq.track_partition = q == 0;
+            const MsdPlan fp = owner_plan(c, nq, K, B1, dup);
+            SortRequest<1> rq = owner_request(dh1, &fp, q == 0, false);
             // the sort's final gather writes the piece's distinct keys straight after the previous pieces' (no
             // append copy: 0.9 ms a rank-step at P = 2 with 4 pieces); CANON is neither its input nor its tmp
             rq.out = acc + off;
@@ -2298,7 +2129,7 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
     // owner of 2 ranks' worth of keys at configs[1]'s density (19 planned bits) keeps a 2-level sort;
     // the counted pass B takes 9
     const unsigned B1 = c.knobs.fused_b1 ? std::max(c.knobs.fused_b1, OB) : (!COUNTED && c.knobs.wide_b1 && d.P >= 2) ? 10u : 9u;
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+    const uint64_t npos = n_windows(in, K);
     c.timings.n_positions = npos;
     constexpr int TILE = ExtractTraits<1>::TILE;
     const uint64_t tiles = ceil_div(npos, TILE);
@@ -2381,7 +2212,7 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
     bool pipe_ok = false;  // the rounds' exchanges pipelined (routed_rounds_pipelined)
     {
         uint64_t want = c.knobs.force_ranges;
-        const double budget = dist_budget(c, d);
+        const double budget = hbm_budget(c, d.coresident);
         const double per_key = 8.0 + (COUNTED ? 4.0 : 0.0);
         if (!want) {
             // one pass: the rank's keys, the received runs and their ping-pong buffer, plus ~3 N of later
@@ -2424,9 +2255,6 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
         c.ws.release_stage_buffers();  // a previous build's would crowd out the rounds' buffers
         *ev_extract = tm.mark();
     }
-    K2 *acc = nullptr;  // rounds: the owned distinct keys so far
-    uint32_t *accc = nullptr;
-    uint64_t off = 0, cap = 0;
     K2 *xa = nullptr;
     uint32_t *xac = nullptr;
     uint64_t U = 0;
@@ -2490,56 +2318,26 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
     // order; returns the distinct keys, left in *pa
     auto owner_sort = [&](K2 **pa, K2 **pb, uint32_t **pac, uint32_t **pbc, uint64_t n1, uint64_t rb0, uint64_t rb1,
                           std::vector<uint32_t> &hown, bool track, bool gidx) -> uint64_t {
-        hown.assign(nb1, 0);
-        uint64_t nown = 0;
-        for (uint32_t i = 0; i < NBH; ++i) {
-            const uint32_t b = i >> (FUSED_HB - B1);
-            if (b >= rb0 && b < rb1) {
-                hown[b] += (uint32_t)H[i];
-                nown += H[i];
-            }
-        }
-        if (nown != n1) throw std::runtime_error("received k-mers differ from the global histogram of the owned range");
+        owner_level1(H, B1, rb0, rb1, hown, n1, "received k-mers differ from the global histogram of the owned range");
         if (!n1) return 0;
         uint32_t *dh1 = (uint32_t *)c.ws.get(Workspace::HIST1, nb1 * 4);
         HIP_CHECK(hipMemcpyAsync(dh1, hown.data(), nb1 * 4, hipMemcpyHostToDevice, c.stream));
         const double spread = (double)nb1 / (double)std::max<uint64_t>(1, rb1 - rb0);
         const double dup = estimate_dup<1>(c, *pa, n1, 8.0) / spread;
-        MsdPlan plan = msd_plan<1>(c, n1, 2 * K, dup);
-        unsigned T = plan.levels ? plan.digit_end[plan.levels] : 0;
-        T = std::min(2 * K, std::max(T, B1 + 1));  // at least one partition pass after the routing digit
-        MsdPlan fp{};
-        fp.levels = 1 + (T - B1 + MSD_DBITS - 1) / MSD_DBITS;
-        fp.digit_end[1] = B1;
-        for (unsigned l = 2; l <= fp.levels; ++l) fp.digit_end[l] = B1 + (T - B1) * (l - 1) / (fp.levels - 1);
-        SortRequest<1> rq;
-        rq.hist1 = dh1;
-        rq.level1_done = true;
-        rq.force_plan = &fp;
-        rq.track_partition = track;
-        rq.want_gidx = gidx;
+        const MsdPlan fp = owner_plan(c, n1, K, B1, dup);
+        SortRequest<1> rq = owner_request(dh1, &fp, track, gidx);
         const uint64_t u = msd_sort_unique<1, COUNTED>(c, pa, pb, pac, pbc, n1, 2 * K, cmax, dup, rq);
         if (gidx) c.build.gidx = rq.gidx;
         return u;
     };
     // the rounds' distinct keys appended to the owned canonical set (sized from the first filled round's
     // share of the owner's range, +25 %)
+    AppendSet<1, COUNTED> set{c, Workspace::CANON, Workspace::CANONC};
     auto append = [&](const K2 *src, const uint32_t *srcc, uint64_t Ur, uint64_t rb0, uint64_t rb1) {
-        if (off + Ur > cap) {
-            uint64_t gr = 0, go = 0;
-            for (uint64_t b = rb0; b < rb1; ++b) gr += gh1[b];
-            for (uint64_t b = ob0; b < ob1; ++b) go += gh1[b];
-            const uint64_t want = off == 0 && gr ? (uint64_t)((double)Ur / (double)gr * (double)go * 1.25) + Ur
-                                                 : (off + Ur) + (off + Ur) / 4;
-            cap = std::max(want, off + Ur);
-            acc = (K2 *)c.ws.get(Workspace::CANON, cap * sizeof(K2), off * sizeof(K2), c.stream);
-            if (COUNTED) accc = (uint32_t *)c.ws.get(Workspace::CANONC, cap * 4, off * 4, c.stream);
-        }
-        if (Ur) {
-            HIP_CHECK(hipMemcpyAsync(acc + off, src, Ur * sizeof(K2), hipMemcpyDeviceToDevice, c.stream));
-            if (COUNTED) HIP_CHECK(hipMemcpyAsync(accc + off, srcc, Ur * 4, hipMemcpyDeviceToDevice, c.stream));
-        }
-        off += Ur;
+        uint64_t gr = 0, go = 0;
+        for (uint64_t b = rb0; b < rb1; ++b) gr += gh1[b];
+        for (uint64_t b = ob0; b < ob1; ++b) go += gh1[b];
+        set.append(src, srcc, Ur, go, gr);
     };
     const bool pipe_rounds = rounds > 1 && d.P > 1 && pipe_ok;
     if (pipe_rounds) {
@@ -2615,13 +2413,7 @@ static bool dist_collect_routed(Ctx &c, Dist &d, unsigned K, bool canonical, uin
         append(xa, xac, Ur, rb0, rb1);
     }
     if (rounds > 1) {
-        if (!acc) {
-            acc = (K2 *)c.ws.get(Workspace::CANON, sizeof(K2));
-            if (COUNTED) accc = (uint32_t *)c.ws.get(Workspace::CANONC, 4);
-        }
-        xa = acc;
-        xac = accc;
-        U = off;
+        U = set.finish(&xa, &xac);
         // the round buffers go before the rc exchange and the dummy stage grow theirs
         for (auto sl : {Workspace::XA, Workspace::XB, Workspace::XAC, Workspace::XBC, Workspace::SPEC_A,
                         Workspace::SPEC_B})
@@ -2646,7 +2438,7 @@ static bool dist_superkmers(Ctx &c, Dist &d, unsigned K, bool canonical, const B
     if (c.knobs.dist_collect != 0 || d.P < 2 || d.P > SK_MAX_OWNERS || K < 20 || K + 16 > (unsigned)SK_KMAX) return false;
     const unsigned M = std::min(11u, K - 12);
     const uint32_t P = (uint32_t)d.P;
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+    const uint64_t npos = n_windows(in, K);
     const uint64_t ntiles = ceil_div(npos, SK_TILE);
     const bool per_read = in.read_counts != nullptr;
     std::vector<std::vector<uint64_t>> soff_r(1, std::vector<uint64_t>(P + 1, 0)), soff_w(1, std::vector<uint64_t>(P + 1, 0));
@@ -2814,7 +2606,7 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
             N = stage_extract<L2, COUNTED>(c, K, canonical, cmax, cin, &ka, &kb, &ca, &cb);
         c.canon_mode = mode_scope.old;
         if (sk) {  // the windows of this rank's reads, not of the received runs
-            T.n_positions = in.seq_len >= K ? in.seq_len - K + 1 : 0;
+            T.n_positions = n_windows(in, K);
         }
         ev_extract = tm.mark();
         tr("extract", N);
@@ -3064,13 +2856,8 @@ static bool want_spill(Ctx &c, unsigned K, bool canonical, const BuildInput &in,
     if (P < 2 || !c.host_output || K < RB_CHARS + 2) return false;
     if (c.knobs.force_spill) return true;
     if (!c.params.disk) return false;
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
-    double budget = c.params.mem_budget;
-    if (budget <= 0) {
-        size_t fr = 0, tot = 0;
-        HIP_CHECK(hipMemGetInfo(&fr, &tot));
-        budget = 0.9 * ((double)fr + (double)c.ws.held());
-    }
+    const uint64_t npos = n_windows(in, K);
+    const double budget = hbm_budget(c);
     const double per_key = (double)sizeof(Key<L2>) + (COUNTED ? 4.0 : 0.0);
     // the in-HBM tail holds the real edges, their flags, the dummies and the output rows
     return (double)npos * (canonical ? 2.0 : 1.0) * (per_key + 4.0) > budget;
@@ -3086,25 +2873,12 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
     mtg_boss_timings &T = c.timings;
     EventTimer tm(c.stream);
     const int ev_start = tm.mark();
-    const uint64_t npos = in.seq_len >= K ? in.seq_len - K + 1 : 0;
-    T.n_positions = npos;
+    T.n_positions = n_windows(in, K);
     const int both = canonical ? 1 : 0;
-    constexpr int TILE = RangeTraits<L2>::TILE;
-    const uint64_t tiles = ceil_div(npos, TILE);
     // the ranges: count pass, bins balanced (collect_ranges)
-    std::vector<uint64_t> hist(RB_BINS, 0);
-    uint16_t *tbins = (uint16_t *)c.ws.get(Workspace::RANGE_BINS, std::max<uint64_t>(tiles, 1) * RB_BINS * 2);
-    if (tiles) {
-        auto *dh = (unsigned long long *)c.ws.get(Workspace::XHIST, RB_BINS * 8);
-        HIP_CHECK(hipMemsetAsync(dh, 0, RB_BINS * 8, c.stream));
-        range_count_kernel<L2><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, both, tbins);
-        HIP_CHECK(hipGetLastError());
-        range_bins_reduce_kernel<<<dim3((unsigned)std::min<uint64_t>(tiles, 2048)), dim3(RB_BINS), 0, c.stream>>>(
-            tbins, tiles, dh);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(hist.data(), dh, RB_BINS * 8, hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipStreamSynchronize(c.stream));
-    }
+    RangeScan<L2> scan(c, in, K, both);
+    std::vector<uint64_t> hist;
+    scan.fetch(c, &hist);
     uint64_t total = 0;
     for (uint64_t v : hist) total += v;
     P = std::min<uint32_t>(P, RB_BINS);
@@ -3112,8 +2886,7 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
     NoComm nocomm((int)P);
     Dist d{nocomm, (int)P, 0, RB_CHARS, 2 * K - 2 * RB_CHARS, RB_BINS, &tm, {}};
     SpillStore st(c.params.disk ? c.params.swap_dir : std::string(), c.params.disk_cap);
-    uint32_t *tcnt = (uint32_t *)c.ws.get(Workspace::DTCNT, (tiles + 1) * 4);
-    uint64_t *toff = (uint64_t *)c.ws.get(Workspace::DTOFF, (tiles + 1) * 8);
+    scan.tile_offsets(c);
     std::vector<uint32_t> eid(P), ecid(P), qid(P);
     std::vector<uint64_t> rn(P, 0);
     std::vector<std::vector<uint64_t>> qpos(P), qcs(P);  // per range: query slices [4][P + 1], class starts [5]
@@ -3122,29 +2895,12 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
         const uint32_t lo = (uint32_t)bounds[j], hi = (uint32_t)bounds[j + 1];
         uint64_t nj = 0;
         for (uint32_t b = lo; b < hi; ++b) nj += hist[b];
-        K2 *ka = (K2 *)c.ws.get(Workspace::KA, std::max<uint64_t>(nj, 1) * sizeof(K2));
-        K2 *kb = (K2 *)c.ws.get(Workspace::KB, std::max<uint64_t>(nj, 1) * sizeof(K2));
-        uint32_t *ca = COUNTED ? (uint32_t *)c.ws.get(Workspace::CA, std::max<uint64_t>(nj, 1) * 4) : nullptr;
-        uint32_t *cb = COUNTED ? (uint32_t *)c.ws.get(Workspace::CB, std::max<uint64_t>(nj, 1) * 4) : nullptr;
-        uint64_t U = 0;
-        if (nj) {
-            BinSet sel{};
-            sel.add(lo, hi);
-            range_tile_counts_kernel<<<dim3((unsigned)ceil_div(tiles, 4)), dim3(256), 0, c.stream>>>(tbins, tiles, sel,
-                                                                                                     tcnt);
-            HIP_CHECK(hipGetLastError());
-            scan_counts(c, tcnt, tiles, toff);
-            range_write_kernel<L2, COUNTED><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(
-                in.seq, in.seq_len, K, both, in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, sel, toff, ka,
-                ca);
-            HIP_CHECK(hipGetLastError());
-            if (read_u64(c, (const unsigned long long *)(toff + tiles)) != nj)
-                throw std::runtime_error("range extraction count differs from its histogram");
-            const double spread = (double)RB_BINS / (double)(hi - lo);
-            const double dup = estimate_dup<L2>(c, ka, nj, 8.0) / spread;
-            SortRequest<L2> rq;
-            U = msd_sort_unique<L2, COUNTED>(c, &ka, &kb, &ca, &cb, nj, 2 * K, cmax, dup, rq);
-        }
+        BinSet sel{};
+        sel.add(lo, hi);
+        K2 *ka, *kb;
+        uint32_t *ca, *cb;
+        const uint64_t U = extract_range_sorted<L2, COUNTED>(c, scan, in, K, both, cmax, sel, nj, false, &ka, &kb, &ca,
+                                                             &cb);
         rn[j] = U;
         eid[j] = st.put(ka, U * sizeof(K2), c.stream);
         if (COUNTED) ecid[j] = st.put(ca, U * 4, c.stream);

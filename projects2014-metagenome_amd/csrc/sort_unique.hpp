@@ -207,6 +207,16 @@ static MsdPlan msd_plan(const Ctx &c, uint64_t n, unsigned nbits, double dup) {
     return p;
 }
 
+// a plan of T bits whose level 1 is fixed at b1 bits (its producer's digit: the fused K1's pass B, the
+// routed collect's routing digit), the rest split evenly over the fewest later levels
+static MsdPlan level1_fixed_plan(unsigned b1, unsigned T) {
+    MsdPlan q{};
+    q.levels = 1 + (T - b1 + MSD_DBITS - 1) / MSD_DBITS;
+    q.digit_end[1] = b1;
+    for (unsigned l = 2; l <= q.levels; ++l) q.digit_end[l] = b1 + (T - b1) * (l - 1) / (q.levels - 1);
+    return q;
+}
+
 // The plan of the rc sort fused with the merge (and of the canonical set's bucket index it reads): u128 keys
 // take one final bit fewer than the unique's plan, so a merge group holds ~480 rc + ~480 canonical keys in
 // its 1024-key LDS arrays instead of ~240 + 240 -- the per-group cost (barriers, table setup) then spreads
