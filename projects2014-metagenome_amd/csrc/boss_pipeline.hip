@@ -43,6 +43,7 @@
 #include "sort_unique.hpp"
 #include "collect_stage.hpp"
 #include "dummy_stage.hpp"
+#include "chunk_host.hpp"
 
 namespace mtg {
 
@@ -58,7 +59,9 @@ struct BuildOutput {
     uint64_t F[5];
     uint64_t n_real;
     uint64_t n_dummy;
-    bool host = false;  // the spilled build (run_pipeline_spill): W / last / weights are host arrays
+    bool host = false;  // the spilled build (run_pipeline_spill): W / last / weights point into the rows below
+    std::vector<uint8_t> host_W, host_last;
+    std::vector<uint32_t> host_weights;
 };
 
 // ---------------------------------------------------------------------------- pipeline stages
@@ -82,12 +85,12 @@ static uint64_t stage_extract(Ctx &c, unsigned K, bool canonical, uint32_t cmax,
         uint32_t *tcnt = (uint32_t *)c.ws.get(Workspace::DTCNT, (tiles + 1) * 4);
         uint64_t *toff = (uint64_t *)c.ws.get(Workspace::DTOFF, (tiles + 1) * 8);
         extract_kernel<L2, COUNTED, true><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(
-            in.seq, in.seq_len, K, cmode(c, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax,
+            in.seq, in.seq_len, K, cmode(in, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax,
             nullptr, nullptr, tcnt, nullptr, nullptr, 0);
         HIP_CHECK(hipGetLastError());
         N = scan_counts_total(c, tcnt, tiles, toff);
         extract_kernel<L2, COUNTED, false><<<dim3((unsigned)tiles), dim3(256), 0, c.stream>>>(
-            in.seq, in.seq_len, K, cmode(c, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax,
+            in.seq, in.seq_len, K, cmode(in, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax,
             *ka, *ca, nullptr, toff, nullptr, 0);
         HIP_CHECK(hipGetLastError());
     }
@@ -122,7 +125,7 @@ static bool stage_extract_windows(Ctx &c, unsigned K, bool canonical, uint32_t c
     HIP_CHECK(hipMemsetAsync(&c.small->wbad, 0, 4, c.stream));
     HIP_CHECK(hipMemsetAsync(&c.small->wcursor, 0, 8, c.stream));
     window_reads_kernel<L2, COUNTED><<<dim3((unsigned)ceil_div(n, 256 * 8)), dim3(256), 0, c.stream>>>(
-        in.seq, in.seq_len, K, cmode(c, canonical), in.read_starts, in.read_counts, n, cmax, *ka,
+        in.seq, in.seq_len, K, cmode(in, canonical), in.read_starts, in.read_counts, n, cmax, *ka,
         COUNTED ? *ca : nullptr, &c.small->wcursor, &c.small->wbad);
     HIP_CHECK(hipGetLastError());
     uint32_t bad = 0;
@@ -209,10 +212,10 @@ static void fused_pass_a(Ctx &c, unsigned K, bool canonical, const BuildInput &i
     // (K > 32: the sampled k-mers need u128 words -- truncated to 64 bits, distinct k-mers collided and
     // the duplication estimate planned too few MSD bits for the u128 rounds)
     if (K > 32)
-        dup_sample_reads_kernel<2><<<dim3(M / 256), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, cmode(c, canonical),
+        dup_sample_reads_kernel<2><<<dim3(M / 256), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, cmode(in, canonical),
                                                                               M, table, SLOTS - 1, table + SLOTS);
     else
-        dup_sample_reads_kernel<1><<<dim3(M / 256), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, cmode(c, canonical),
+        dup_sample_reads_kernel<1><<<dim3(M / 256), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, cmode(in, canonical),
                                                                               M, table, SLOTS - 1, table + SLOTS);
     HIP_CHECK(hipGetLastError());
     constexpr int TILE = ExtractTraits<1>::TILE;
@@ -254,13 +257,13 @@ static void fused_pass_a(Ctx &c, unsigned K, bool canonical, const BuildInput &i
     }
     if (K > 32) {
         if (K == 63 && c.knobs.kspec)
-            extract_hist_wide_kernel<63><<<dim3(nrows), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, cmode(c, canonical),
+            extract_hist_wide_kernel<63><<<dim3(nrows), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, cmode(in, canonical),
                                                                               tiles, per_row, rows, sample);
         else
-            extract_hist_wide_kernel<0><<<dim3(nrows), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, cmode(c, canonical),
+            extract_hist_wide_kernel<0><<<dim3(nrows), dim3(256), 0, c.stream>>>(in.seq, in.seq_len, K, cmode(in, canonical),
                                                                              tiles, per_row, rows, sample);
     } else {
-        launch_hist_fast<false>(c, K, dim3(nrows), dim3(256), in.seq, in.seq_len, K, cmode(c, canonical), tiles, per_row,
+        launch_hist_fast<false>(c, K, dim3(nrows), dim3(256), in.seq, in.seq_len, K, cmode(in, canonical), tiles, per_row,
                                 rows, (uint32_t *)nullptr, sample);
     }
     HIP_CHECK(hipGetLastError());
@@ -300,8 +303,8 @@ struct BucketSel {
 
 // the u128 pass B as the packed-word kernel (extract_partition_fast2_kernel): uncounted basic / canonical
 template <int L, bool COUNTED>
-static inline bool fast2_applies(const Ctx &c, unsigned K, bool canonical) {
-    return L == 2 && !COUNTED && c.knobs.fast2 && K > 32 && K <= 64 && cmode(c, canonical) <= 1;
+static inline bool fast2_applies(const Ctx &c, unsigned K, bool canonical, const BuildInput &in) {
+    return L == 2 && !COUNTED && c.knobs.fast2 && K > 32 && K <= 64 && cmode(in, canonical) <= 1;
 }
 
 // pass B: the k-mers whose level-1 bucket (top b1 bits) is in `sel` (nullptr: every bucket)
@@ -351,7 +354,7 @@ static uint64_t fused_pass_b(Ctx &c, unsigned K, bool canonical, uint32_t cmax, 
     EventTimer tm(c.stream);
     tm.mark();
     const bool fast_b = L == 1 && !COUNTED && K <= 32;
-    if (bdelta && !fast_b && !fast2_applies<L, COUNTED>(c, K, canonical))
+    if (bdelta && !fast_b && !fast2_applies<L, COUNTED>(c, K, canonical, in))
         throw std::runtime_error("per-bucket destinations need the u64 or the packed-word u128 pass B");
     if constexpr (L == 2) {
         // u128 windows (K <= 64): pass B on 256-thread tiles (A was made for them); uncounted canonical /
@@ -359,47 +362,47 @@ static uint64_t fused_pass_b(Ctx &c, unsigned K, bool canonical, uint32_t cmax, 
         constexpr int B = fused_block<2>();
         if (b1 > 9) throw std::runtime_error("the u128 pass B takes at most 9 bits");
         const uint64_t ftiles = ceil_div(A.npos, FusedTraits<COUNTED, B>::TILE);
-        if (fast2_applies<L, COUNTED>(c, K, canonical)) {
+        if (fast2_applies<L, COUNTED>(c, K, canonical, in)) {
             // the same 4096-window tiles as 512 threads of 8 windows (twice the waves a CU at the same LDS)
             static_assert(FusedTraits<COUNTED, B>::TILE == 512 * 8, "a pass-B tile = 512 threads x 8 windows");
             if (c.knobs.fast2_ppt8 && K == 63 && c.knobs.kspec)
                 extract_partition_fast2_kernel<512, 63, 8><<<dim3((unsigned)xcd_grid(ftiles)), dim3(512), 0, c.stream>>>(
-                    in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
+                    in.seq, in.seq_len, K, cmode(in, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
                     (const uint32_t *)dsel, bdelta);
             else if (c.knobs.fast2_ppt8)
                 extract_partition_fast2_kernel<512, 0, 8><<<dim3((unsigned)xcd_grid(ftiles)), dim3(512), 0, c.stream>>>(
-                    in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
+                    in.seq, in.seq_len, K, cmode(in, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
                     (const uint32_t *)dsel, bdelta);
             else if (K == 63 && c.knobs.kspec)
                 extract_partition_fast2_kernel<B, 63><<<dim3((unsigned)xcd_grid(ftiles)), dim3(B), 0, c.stream>>>(
-                    in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
+                    in.seq, in.seq_len, K, cmode(in, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
                     (const uint32_t *)dsel, bdelta);
             else
                 extract_partition_fast2_kernel<B><<<dim3((unsigned)xcd_grid(ftiles)), dim3(B), 0, c.stream>>>(
-                    in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
+                    in.seq, in.seq_len, K, cmode(in, canonical), b1, A.per_stripe, scur, send, (Key<2> *)ka, &c.small->error,
                     (const uint32_t *)dsel, bdelta);
         } else if (K == 63 && c.knobs.kspec)
             extract_partition_kernel<2, COUNTED, B, 63><<<dim3((unsigned)xcd_grid(ftiles)), dim3(B), 0, c.stream>>>(
-                in.seq, in.seq_len, K, cmode(c, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, b1,
+                in.seq, in.seq_len, K, cmode(in, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, b1,
                 A.per_stripe, scur, send, ka, COUNTED ? ca : nullptr, &c.small->error, dsel);
         else
             extract_partition_kernel<2, COUNTED, B><<<dim3((unsigned)xcd_grid(ftiles)), dim3(B), 0, c.stream>>>(
-                in.seq, in.seq_len, K, cmode(c, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, b1,
+                in.seq, in.seq_len, K, cmode(in, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, b1,
                 A.per_stripe, scur, send, ka, COUNTED ? ca : nullptr, &c.small->error, dsel);
     } else if (fast_b) {
         constexpr int B = 512;
         const dim3 g((unsigned)xcd_grid(ceil_div(A.npos, 16 * B)));
         if (b1 > 9)
-            launch_part_fast<B, 1024>(c, K, g, dim3(B), in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur,
+            launch_part_fast<B, 1024>(c, K, g, dim3(B), in.seq, in.seq_len, K, cmode(in, canonical), b1, A.per_stripe, scur,
                                       send, ka, &c.small->error, (const uint32_t *)dsel, (uint32_t *)nullptr, bdelta);
         else
-            launch_part_fast<B, 512>(c, K, g, dim3(B), in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur,
+            launch_part_fast<B, 512>(c, K, g, dim3(B), in.seq, in.seq_len, K, cmode(in, canonical), b1, A.per_stripe, scur,
                                      send, ka, &c.small->error, (const uint32_t *)dsel, (uint32_t *)nullptr, bdelta);
     } else {
         if (b1 > 9) throw std::runtime_error("the counted pass B takes at most 9 bits");
         const uint64_t ftiles = ceil_div(A.npos, FusedTraits<COUNTED, 512>::TILE);
         extract_partition_kernel<1, COUNTED, 512><<<dim3((unsigned)xcd_grid(ftiles)), dim3(512), 0, c.stream>>>(
-            in.seq, in.seq_len, K, cmode(c, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, b1,
+            in.seq, in.seq_len, K, cmode(in, canonical), in.read_starts, in.read_counts, in.n_reads, in.rid_at, cmax, b1,
             A.per_stripe, scur, send, (Key<1> *)ka, COUNTED ? ca : nullptr, &c.small->error, dsel);
     }
     HIP_CHECK(hipGetLastError());
@@ -454,10 +457,10 @@ static uint64_t fused_pass_b_spec(Ctx &c, unsigned K, bool canonical, const Buil
     constexpr int B = 512;
     const dim3 g((unsigned)xcd_grid(ceil_div(A.npos, 16 * B)));
     if (b1 > 9)
-        launch_part_fast<B, 1024>(c, K, g, dim3(B), in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send,
+        launch_part_fast<B, 1024>(c, K, g, dim3(B), in.seq, in.seq_len, K, cmode(in, canonical), b1, A.per_stripe, scur, send,
                                   *ka, &c.small->error, (const uint32_t *)nullptr, &c.small->spec_ovf);
     else
-        launch_part_fast<B, 512>(c, K, g, dim3(B), in.seq, in.seq_len, K, cmode(c, canonical), b1, A.per_stripe, scur, send,
+        launch_part_fast<B, 512>(c, K, g, dim3(B), in.seq, in.seq_len, K, cmode(in, canonical), b1, A.per_stripe, scur, send,
                                  *ka, &c.small->error, (const uint32_t *)nullptr, &c.small->spec_ovf);
     HIP_CHECK(hipGetLastError());
     tm.mark();
@@ -733,7 +736,8 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     // learned to carve pieces off its kept blocks, Workspace::take_cached)
     bool one_b = false;
     // (u128, configs[2]: both rounds' keys, 141 GB, beside KB and the canonical set -- ~255 of the 309 GB)
-    if (R == 2 && c.knobs.rounds_one_b && ((L == 1 && !COUNTED && K <= 32) || fast2_applies<L, COUNTED>(c, K, canonical))) {
+    if (R == 2 && c.knobs.rounds_one_b &&
+        ((L == 1 && !COUNTED && K <= 32) || fast2_applies<L, COUNTED>(c, K, canonical, in))) {
         const double kb = (double)sizeof(K2);
         const double need = ((double)N + (double)nmax) * kb + u_est * 1.25 * kb + (double)(1ull << 30);
         one_b = need <= budget;
@@ -2593,18 +2597,12 @@ static void run_pipeline_dist(Ctx &c, Comm &comm, unsigned k, bool canonical, un
         // a super-k-mer owner keeps the representative whose top bits hash smaller (cmode 2): its keys
         // spread evenly over the key space instead of piling up at small prefixes (min(fwd, rc)), so the
         // local sort's buckets do not overflow, and the range owners' shares stay even
-        struct ModeScope {
-            Ctx &c;
-            int old;
-            ~ModeScope() { c.canon_mode = old; }
-        } mode_scope{c, c.canon_mode};
-        if (sk && d.P > 1) c.canon_mode = 2;
+        if (sk && d.P > 1) sk_in.canon_mode = 2;
         if (stage_extract_windows<L2, COUNTED>(c, K, canonical, cmax, cin, &ka, &kb, &ca, &cb, &N))
             dup = 1.0;
         else if (!stage_extract_fused<L2, COUNTED>(c, K, canonical, cmax, cin, &ka, &kb, &ca, &cb, &N, &dup, &rq,
                                                     &fplan))
             N = stage_extract<L2, COUNTED>(c, K, canonical, cmax, cin, &ka, &kb, &ca, &cb);
-        c.canon_mode = mode_scope.old;
         if (sk) {  // the windows of this rank's reads, not of the received runs
             T.n_positions = n_windows(in, K);
         }
@@ -2853,7 +2851,7 @@ class NoComm : public Comm {
 // the windows of both strands) may not fit the budget -- or always with MTG_SPILL=1
 template <int L2, bool COUNTED>
 static bool want_spill(Ctx &c, unsigned K, bool canonical, const BuildInput &in, uint32_t P) {
-    if (P < 2 || !c.host_output || K < RB_CHARS + 2) return false;
+    if (P < 2 || !c.build.host_output || K < RB_CHARS + 2) return false;
     if (c.knobs.force_spill) return true;
     if (!c.params.disk) return false;
     const uint64_t npos = n_windows(in, K);
@@ -2961,9 +2959,6 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
     }
     const int ev_dummy_route = tm.mark();
     // ---- 3. per range: dummies sorted, rows emitted, appended on the host
-    c.spill_W.clear();
-    c.spill_last.clear();
-    c.spill_weights.clear();
     uint64_t F[5] = {0, 0, 0, 0, 0}, ndummy = 0;
     for (uint32_t r = 0; r < P; ++r) {
         const uint64_t Rr = rn[r];
@@ -2992,14 +2987,14 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
         check_error_word(c);
         // extend: range 0 keeps its leading row 0, the others append the rows after it
         const uint64_t from = r == 0 ? 0 : 1, rows = o2.n - from;
-        const uint64_t at = c.spill_W.size();
-        c.spill_W.resize(at + rows);
-        c.spill_last.resize(at + rows);
-        HIP_CHECK(hipMemcpyAsync(c.spill_W.data() + at, o2.W + from, rows, hipMemcpyDeviceToHost, c.stream));
-        HIP_CHECK(hipMemcpyAsync(c.spill_last.data() + at, o2.last + from, rows, hipMemcpyDeviceToHost, c.stream));
+        const uint64_t at = out->host_W.size();
+        out->host_W.resize(at + rows);
+        out->host_last.resize(at + rows);
+        HIP_CHECK(hipMemcpyAsync(out->host_W.data() + at, o2.W + from, rows, hipMemcpyDeviceToHost, c.stream));
+        HIP_CHECK(hipMemcpyAsync(out->host_last.data() + at, o2.last + from, rows, hipMemcpyDeviceToHost, c.stream));
         if (COUNTED) {
-            c.spill_weights.resize(at + rows);
-            HIP_CHECK(hipMemcpyAsync(c.spill_weights.data() + at, o2.weights + from, rows * 4, hipMemcpyDeviceToHost,
+            out->host_weights.resize(at + rows);
+            HIP_CHECK(hipMemcpyAsync(out->host_weights.data() + at, o2.weights + from, rows * 4, hipMemcpyDeviceToHost,
                                      c.stream));
         }
         HIP_CHECK(hipStreamSynchronize(c.stream));
@@ -3009,14 +3004,13 @@ static void run_pipeline_spill(Ctx &c, unsigned k, bool canonical, unsigned bits
     const int ev_emit = tm.mark();
     HIP_CHECK(hipStreamSynchronize(c.stream));
     out->host = true;
-    out->W = c.spill_W.data();
-    out->last = c.spill_last.data();
-    out->weights = COUNTED ? c.spill_weights.data() : nullptr;
-    out->n = c.spill_W.size();
+    out->W = out->host_W.data();
+    out->last = out->host_last.data();
+    out->weights = COUNTED ? out->host_weights.data() : nullptr;
+    out->n = out->host_W.size();
     std::memcpy(out->F, F, sizeof(F));
     out->n_real = R;
     out->n_dummy = ndummy;
-    c.spilled_bytes = st.total();
     T.spilled_bytes = st.total();
     T.n_dummy = ndummy;
     T.n_rows = out->n;
@@ -3200,6 +3194,10 @@ static void run_dispatch(Ctx &c, Comm *comm, unsigned k, bool canonical, unsigne
 }
 }  // namespace mtg
 
+// the driver of the device graph writer: included here, after the pipelines, so that the kernels it is the
+// first to instantiate stay last in the code object and the pipelines' kernels keep their places in it
+#include "dbg_device_write.hpp"
+
 // ============================================================================ C ABI
 
 struct mtg_boss_ctor {
@@ -3214,62 +3212,29 @@ struct mtg_boss_ctor {
     std::atomic<uint64_t> stage_ns{0};  // host time spent staging since the last build
     std::mutex fa_mu;
     std::vector<mtg::FastaInput> fasta;  // FASTA / FASTQ files, split into reads on the device
-    uint8_t *w4_host = nullptr;          // pinned landing buffer of the 4-bit W copy
-    uint64_t w4_cap = 0;
-    uint8_t *wn_host = nullptr;          // pinned landing buffer of the narrowed weights copy
-    uint64_t wn_cap = 0;
+    mtg::PinnedLanding land_w4, land_wn;  // where the 4-bit W and the narrowed weights land (chunk_host.hpp)
     ~mtg_boss_ctor() {
         for (auto &f : fasta) mtg::free_fasta(f);
-        if (w4_host) (void)hipHostFree(w4_host);
-        if (wn_host) (void)hipHostFree(wn_host);
     }
 };
 
-// staged reads (host_stage.hpp) -> one byte per char: ACGT, or 'N' for every char that breaks a
-// k-mer window (separators, alignment gaps, N and the rest); one 32-char word per thread
-__global__ void unpack_reads_kernel(const uint64_t *__restrict__ codes, const uint32_t *__restrict__ valid,
-                                    uint64_t nw, uint8_t *__restrict__ out) {
-    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= nw) return;
-    const uint64_t c = codes[w];
-    const uint32_t v = valid[w];
-    uint32_t o[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        uint32_t word = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int j = 4 * q + b;
-            const uint32_t ch = (v >> j) & 1u ? (0x54474341u >> (8 * ((c >> (2 * j)) & 3u))) & 0xFFu : (uint32_t)'N';
-            word |= ch << (8 * b);
-        }
-        o[q] = word;
-    }
-    uint4 *dst = (uint4 *)(out + 32 * w);
-    dst[0] = make_uint4(o[0], o[1], o[2], o[3]);
-    dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
-}
-
-// one packed `last` word per thread: bit j of word w = last[64 w + j] (sdsl bit_vector layout)
-__global__ void pack_bits_kernel(const uint8_t *__restrict__ bytes, uint64_t n, uint64_t *__restrict__ words) {
-    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t i0 = w * 64;
-    if (i0 >= n) return;
-    uint64_t v = 0;
-    if (i0 + 64 <= n && ((uintptr_t)(bytes + i0) & 7) == 0) {
-        const uint64_t *p = reinterpret_cast<const uint64_t *>(bytes + i0);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const uint64_t x = p[q];  // 8 flag bytes (0/1) -> 8 bits
-            v |= ((x * 0x0102040810204080ull) >> 56 & 0xFFull) << (8 * q);
-        }
-    } else {
-        for (uint64_t j = 0; j < 64 && i0 + j < n; ++j) v |= (uint64_t)(bytes[i0 + j] & 1) << j;
-    }
-    words[w] = v;
-}
-
 using namespace mtg;
+
+// the ABI's error boundary: what f throws becomes the thread's error text and the entry point's own code
+template <class F>
+static int abi_call(int on_throw, F &&f) {
+    try {
+        return f();
+    } catch (const std::exception &e) {
+        set_error(e.what());
+        return on_throw;
+    }
+}
+
+static int bad_arguments(const char *msg = "bad arguments") {
+    set_error(msg);
+    return MTG_ERR_ARGUMENT;
+}
 
 extern "C" {
 
@@ -3344,12 +3309,9 @@ void mtg_boss_ctor_destroy(mtg_boss_ctor *c) {
 uint64_t mtg_boss_ctor_get_k(const mtg_boss_ctor *c) { return c ? c->params.k : 0; }
 
 int mtg_boss_ctor_trim(mtg_boss_ctor *c) {
-    if (!c) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (!c) return bad_arguments();
     std::lock_guard<std::mutex> lock(c->mu);
-    try {
+    return abi_call(MTG_ERR_DEVICE, [&] {
         HIP_CHECK(hipSetDevice(c->device));
         // the last build's stage buffers too (its device chunk arrays stay valid): a configs[2] build
         // holds ~200 GB in them, and a second constructor in the same process had 110 MiB left
@@ -3357,10 +3319,7 @@ int mtg_boss_ctor_trim(mtg_boss_ctor *c) {
         c->ctx.ws.drop_cache();
         c->ctx.timings.cached_bytes = 0;
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_DEVICE;
-    }
+    });
 }
 
 struct StageTimer {
@@ -3378,58 +3337,40 @@ static unsigned stage_threads(const mtg_boss_ctor *c) {
 
 int mtg_boss_ctor_add_sequences(mtg_boss_ctor *c, const char *const *seqs, const uint64_t *lens,
                                 const uint64_t *counts, size_t n) {
-    if (!c || (n && (!seqs || !lens))) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
-    try {
+    if (!c || (n && (!seqs || !lens))) return bad_arguments();
+    return abi_call(MTG_ERR_ARGUMENT, [&] {
         StageTimer t{c->stage_ns};
         c->stage.add(seqs, lens, counts, n, stage_threads(c));
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_ARGUMENT;
-    }
+    });
 }
 
 int mtg_boss_ctor_add_sequence(mtg_boss_ctor *c, const char *seq, uint64_t len, uint64_t count) {
-    if (!c || (len && !seq)) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (!c || (len && !seq)) return bad_arguments();
     const char *p = seq ? seq : "";
     return mtg_boss_ctor_add_sequences(c, &p, &len, &count, 1);
 }
 
 int mtg_boss_ctor_add_packed(mtg_boss_ctor *c, const char *data, const uint64_t *offsets,
                              const uint64_t *counts, size_t n) {
-    if (!c || (n && (!data || !offsets))) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (!c || (n && (!data || !offsets))) return bad_arguments();
     for (size_t i = 0; i < n; ++i) {
         if (offsets[i + 1] < offsets[i]) {
             set_error("offsets must be nondecreasing");
             return MTG_ERR_ARGUMENT;
         }
     }
-    try {
+    return abi_call(MTG_ERR_ARGUMENT, [&] {
         StageTimer t{c->stage_ns};
         c->stage.add_packed(data, offsets, counts, n, stage_threads(c));
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_ARGUMENT;
-    }
+    });
 }
 
 int mtg_boss_ctor_add_kmc(mtg_boss_ctor *c, const char *kmc_path, uint64_t min_count, uint64_t max_count,
                           int call_both_from_canonical) {
-    if (!c || !kmc_path) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
-    try {
+    if (!c || !kmc_path) return bad_arguments();
+    return abi_call(MTG_ERR_ARGUMENT, [&] {
         // the first database of a batch is copied to the device while its files are read (the
         // workspace's KMC slots; a later database is copied by build_chunk, the slots being taken)
         std::unique_lock<std::mutex> lock(c->kmc_mu, std::defer_lock);
@@ -3446,28 +3387,19 @@ int mtg_boss_ctor_add_kmc(mtg_boss_ctor *c, const char *kmc_path, uint64_t min_c
         if (!lock.owns_lock()) lock.lock();
         if (in.total) c->kmc.push_back(std::move(in));
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_ARGUMENT;
-    }
+    });
 }
 
 int mtg_boss_ctor_add_fasta(mtg_boss_ctor *c, const char *path) {
-    if (!c || !path) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
-    try {
+    if (!c || !path) return bad_arguments();
+    return abi_call(MTG_ERR_ARGUMENT, [&] {
         StageTimer t{c->stage_ns};
         FastaInput in = load_fasta_file(path);  // read + inflate in the caller's thread
         std::lock_guard<std::mutex> lock(c->fa_mu);
         if (in.size) c->fasta.push_back(in);
         else free_fasta(in);
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_ARGUMENT;
-    }
+    });
 }
 
 // the staged FASTA / FASTQ files -> reads appended to dseq at *seq_base (fasta.hpp); with
@@ -3549,8 +3481,11 @@ static const char *kSuffixDist =
     "the suffix-filtered route builds one chunk per suffix on one GPU; it has no multi-GPU form";
 
 // the build on the device buffers: the suffix route or the full construction
-static void dispatch_build(mtg_boss_ctor *c, mtg::Comm *comm, const BuildInput &in_, BuildOutput *out) {
+// (host_output: the arrays go to the host, so a single build may spill)
+static void dispatch_build(mtg_boss_ctor *c, mtg::Comm *comm, const BuildInput &in_, bool host_output,
+                           BuildOutput *out) {
     mtg::reset_build_state(c->ctx);  // nothing of the previous build (a failed one included) is carried over
+    c->ctx.build.host_output = host_output;
     BuildInput in = in_;
     if (in.read_counts && in.n_reads > 1) {  // bracket the per-read count searches (device_common.hpp)
         const uint64_t nq = (in.seq_len >> mtg::RID_SHIFT) + 2;
@@ -3578,7 +3513,7 @@ static int run_build(mtg_boss_ctor *c, mtg::Comm *comm, const BuildInput &in, Bu
         set_error(kSuffixDist);
         return MTG_ERR_UNSUPPORTED;
     }
-    try {
+    return abi_call(MTG_ERR_DEVICE, [&] {
         HIP_CHECK(hipSetDevice(c->device));
         // the build's device work, bracketed for the exchange layer (LocalComm's serial mode)
         struct Scope {
@@ -3589,21 +3524,15 @@ static int run_build(mtg_boss_ctor *c, mtg::Comm *comm, const BuildInput &in, Bu
             }
         } scope{comm, c->ctx.stream};
         if (comm) comm->begin_build(c->ctx.stream);
-        dispatch_build(c, comm, in, out);
+        dispatch_build(c, comm, in, false, out);
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_DEVICE;
-    }
+    });
 }
 
 static int build_device_impl(mtg_boss_ctor *c, mtg::Comm *comm, const uint8_t *d_seq, uint64_t seq_len,
                              const uint64_t *d_read_starts, const uint32_t *d_counts, uint64_t n_reads,
                              void *stream, mtg_boss_device_chunk *out) {
-    if (!c || !out || (seq_len && !d_seq) || (!d_read_starts != !d_counts)) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (!c || !out || (seq_len && !d_seq) || (!d_read_starts != !d_counts)) return bad_arguments();
     std::lock_guard<std::mutex> lock(c->mu);
     hipStream_t saved = c->ctx.stream;
     if (stream) c->ctx.stream = (hipStream_t)stream;
@@ -3623,209 +3552,154 @@ static int build_device_impl(mtg_boss_ctor *c, mtg::Comm *comm, const uint8_t *d
     return MTG_OK;
 }
 
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
+// the inputs of one build_chunk batch on the device, and what getting them there took
+struct StagedInput {
+    BuildInput in;
+    double h2d_ms, input_ms;
+};
 
-// W (values 0..9) crosses PCIe as 4-bit codes: packed on the device, copied in pieces, and
-// unpacked by the host threads as the pieces land (half the bytes of the largest D2H)
-__global__ void pack_w4_kernel(const uint8_t *__restrict__ w, uint64_t n, uint8_t *__restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;  // 16 output bytes each
-    const uint64_t b0 = i * 32;
-    if (b0 >= n) return;
-    uint32_t o[4] = {0, 0, 0, 0};
-    if (b0 + 32 <= n) {
-        const uint4 a = *(const uint4 *)(w + b0), b = *(const uint4 *)(w + b0 + 16);
-        const uint32_t in[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {  // 4 W bytes -> 2 packed bytes
-            const uint32_t v = in[q];
-            const uint32_t p = (v & 0xF) | ((v >> 4) & 0xF0) | (((v >> 16) & 0xF) << 8) | (((v >> 24) & 0xF) << 12);
-            o[q / 2] |= p << (16 * (q & 1));
-        }
-    } else {
-        for (uint64_t j = b0; j < n; ++j) {
-            const uint32_t k = (uint32_t)(j - b0);
-            o[k / 8] |= (uint32_t)(w[j] & 0xF) << (4 * (k % 8));
-        }
-    }
-    const uint64_t nb = (n + 1) / 2, ob = b0 / 2;
-    if (ob + 16 <= nb) {
-        *(uint4 *)(out + ob) = make_uint4(o[0], o[1], o[2], o[3]);
-    } else {
-        for (uint64_t j = ob; j < nb; ++j) out[j] = (uint8_t)(o[(j - ob) / 4] >> (8 * ((j - ob) % 4)));
-    }
-}
-
-__attribute__((target("avx2"))) static void unpack_w4_avx2(const uint8_t *in, uint64_t nbytes, uint8_t *out) {
-    uint64_t i = 0;
-    const __m256i m = _mm256_set1_epi8(0x0F);
-    for (; i + 32 <= nbytes; i += 32) {
-        const __m256i v = _mm256_loadu_si256((const __m256i *)(in + i));
-        const __m256i lo = _mm256_and_si256(v, m), hi = _mm256_and_si256(_mm256_srli_epi16(v, 4), m);
-        const __m256i a = _mm256_unpacklo_epi8(lo, hi), b = _mm256_unpackhi_epi8(lo, hi);
-        _mm256_storeu_si256((__m256i *)(out + 2 * i), _mm256_permute2x128_si256(a, b, 0x20));
-        _mm256_storeu_si256((__m256i *)(out + 2 * i + 32), _mm256_permute2x128_si256(a, b, 0x31));
-    }
-    for (; i < nbytes; ++i) {
-        out[2 * i] = in[i] & 0xF;
-        out[2 * i + 1] = in[i] >> 4;
-    }
-}
-
-static void unpack_w4(const uint8_t *in, uint64_t nbytes, uint8_t *out) {
-    if (__builtin_cpu_supports("avx2")) return unpack_w4_avx2(in, nbytes, out);
-    for (uint64_t i = 0; i < nbytes; ++i) {
-        out[2 * i] = in[i] & 0xF;
-        out[2 * i + 1] = in[i] >> 4;
-    }
-}
-
-// W[0..n) on the device -> host W (out, n bytes): 4-bit pieces of 16 MiB, unpacked as they land
-static void copy_w_to_host(mtg_boss_ctor *c, const uint8_t *dW, uint64_t n, uint8_t *out) {
-    if (!n) return;
+// one H2D copy of the pinned read buffer with its starts and counts, then the KMC records decoded and the
+// FASTA / FASTQ files split into reads behind it, on the device
+static StagedInput stage_inputs(mtg_boss_ctor *c) {
     hipStream_t s = c->ctx.stream;
-    if (n < (128ull << 20)) {  // small W: one plain copy (the pieces' sync and thread costs do not pay)
-        HIP_CHECK(hipMemcpyAsync(out, dW, n, hipMemcpyDeviceToHost, s));
-        return;
+    HostStage &st = c->stage;
+    const uint64_t len = st.size();
+    const uint64_t nr = st.n_reads();
+    uint64_t kmc_bytes = 0, kmc_reads = 0;
+    for (const auto &m : c->kmc) {
+        kmc_bytes += m.total * (m.k + 1) * (m.both ? 2 : 1);
+        kmc_reads += m.total * (m.both ? 2 : 1);
     }
-    const uint64_t nb = (n + 1) / 2;
-    uint8_t *d4 = (uint8_t *)c->ctx.ws.get(Workspace::W4, nb + 16);
-    pack_w4_kernel<<<dim3((unsigned)ceil_div(ceil_div(n, 32), 256)), dim3(256), 0, s>>>(dW, n, d4);
-    HIP_CHECK(hipGetLastError());
-    if (c->w4_cap < nb + 16) {  // the ctor's pinned landing buffer, grown on demand
-        if (c->w4_host) (void)hipHostFree(c->w4_host);
-        c->w4_host = nullptr;
-        c->w4_cap = 0;
-        HIP_CHECK(hipHostMalloc((void **)&c->w4_host, nb + nb / 4 + 16, hipHostMallocDefault));
-        c->w4_cap = nb + nb / 4 + 16;
+    uint64_t fa_bytes = 0, fa_reads = 0;
+    for (const auto &f : c->fasta) fa_bytes += f.size + 1;  // split output <= raw bytes + a separator
+    const bool per_read_inputs = st.any_count_not_one() || kmc_reads;
+    if (c->params.bits_per_count && per_read_inputs && !c->fasta.empty()) {
+        uint64_t sb = 0;  // record counts first: the read-start arrays are sized by them
+        split_fasta_files(c, nullptr, &sb, nullptr, nullptr, &fa_reads, true);
     }
-    uint8_t *h4 = c->w4_host;
-    constexpr uint64_t PIECE = 16ull << 20;  // packed bytes per piece
-    const uint64_t np = ceil_div(nb, PIECE);
-    std::vector<hipEvent_t> ev(np);
-    for (uint64_t p = 0; p < np; ++p) {
-        const uint64_t b0 = p * PIECE, len = std::min(PIECE, nb - b0);
-        HIP_CHECK(hipEventCreateWithFlags(&ev[p], hipEventDisableTiming));
-        HIP_CHECK(hipMemcpyAsync(h4 + b0, d4 + b0, len, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipEventRecord(ev[p], s));
-    }
-    const unsigned T = std::max(1u, std::min<unsigned>(stage_threads(c), (unsigned)np));
-    std::atomic<bool> failed{false};
-    parallel_ranges(T, T, 1, [&](uint64_t t0, uint64_t t1) {
-        DeviceGuard g(c->device);
-        for (uint64_t t = t0; t < t1; ++t)
-            for (uint64_t p = t; p < np; p += T) {
-                if (hipEventSynchronize(ev[p]) != hipSuccess) {
-                    failed = true;
-                    return;
-                }
-                const uint64_t b0 = p * PIECE, len = std::min(PIECE, nb - b0);
-                // the last packed byte of an odd n holds one W value
-                const uint64_t full = (b0 + len == nb && (n & 1)) ? len - 1 : len;
-                unpack_w4(h4 + b0, full, out + 2 * b0);
-                if (full < len) out[2 * (b0 + full)] = h4[b0 + full] & 0xF;
-            }
-    });
-    for (auto e : ev) (void)hipEventDestroy(e);
-    if (failed) throw std::runtime_error("W copy to the host failed");
-}
-
-// u32 weights (already clamped to the count width) -> `bytes` (1 or 2) per weight, 16 weights a thread
-__global__ void narrow_weights_kernel(const uint32_t *__restrict__ w, uint64_t n, unsigned bytes,
-                                      uint8_t *__restrict__ out) {
-    const uint64_t i0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    if (i0 >= n) return;
-    if (i0 + 16 <= n) {
-        const uint4 *src = (const uint4 *)(w + i0);
-        uint32_t v[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint4 a = src[q];
-            v[4 * q] = a.x, v[4 * q + 1] = a.y, v[4 * q + 2] = a.z, v[4 * q + 3] = a.w;
+    const uint64_t total_len = len + kmc_bytes + fa_bytes, total_reads = nr + kmc_reads + fa_reads;
+    const auto t_h2d = std::chrono::steady_clock::now();
+    uint8_t *dseq = (uint8_t *)c->ctx.ws.get(Workspace::SEQ, total_len + 1);
+    if (len) {
+        // the staged 2-bit codes + valid mask: on the device already (the stage's mirror, copied
+        // while the reads were staged), else copied now; unpacked to one byte per char
+        const uint64_t nw = len / 32;
+        const uint64_t *dcodes = nullptr;
+        const uint32_t *dvalid = nullptr;
+        if (!st.mirror_wait(&dcodes, &dvalid)) {
+            uint64_t *pk = (uint64_t *)c->ctx.ws.get(Workspace::PACKED, nw * 12);
+            HIP_CHECK(hipMemcpyAsync(pk, st.codes(), nw * 8, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(pk + nw, st.valid(), nw * 4, hipMemcpyHostToDevice, s));
+            dcodes = pk;
+            dvalid = (const uint32_t *)(pk + nw);
         }
-        if (bytes == 1) {
-            uint32_t o[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                o[q] = (v[4 * q] & 0xFF) | (v[4 * q + 1] & 0xFF) << 8 | (v[4 * q + 2] & 0xFF) << 16 | v[4 * q + 3] << 24;
-            *(uint4 *)(out + i0) = make_uint4(o[0], o[1], o[2], o[3]);
+        unpack_reads_kernel<<<dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, s>>>(dcodes, dvalid, nw, dseq);
+        HIP_CHECK(hipGetLastError());
+    }
+    uint64_t *dstarts = nullptr;
+    uint32_t *dcounts = nullptr;
+    const bool per_read = c->params.bits_per_count && per_read_inputs && total_reads;
+    if (per_read) {
+        dstarts = (uint64_t *)c->ctx.ws.get(Workspace::STARTS, total_reads * 8);
+        dcounts = (uint32_t *)c->ctx.ws.get(Workspace::RCOUNTS, total_reads * 4);
+        if (nr) {
+            HIP_CHECK(hipMemcpyAsync(dstarts, st.starts().data(), nr * 8, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(dcounts, st.counts().data(), nr * 4, hipMemcpyHostToDevice, s));
+        }
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    const double h2d_ms = ms_since(t_h2d);
+    // KMC records -> reads, on the device (kmc.hpp)
+    const auto t_input = std::chrono::steady_clock::now();
+    uint64_t seq_base = len, read_base = nr;
+    for (const auto &m : c->kmc) {
+        const uint64_t *dlut;
+        const uint8_t *drec;
+        if (m.dpre) {  // copied while add_kmc read the files (same stream)
+            dlut = (const uint64_t *)(m.dpre + 8);
+            drec = m.dsuf + 8;
         } else {
-            uint32_t o[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) o[q] = (v[2 * q] & 0xFFFF) | v[2 * q + 1] << 16;
-            *(uint4 *)(out + 2 * i0) = make_uint4(o[0], o[1], o[2], o[3]);
-            *(uint4 *)(out + 2 * i0 + 16) = make_uint4(o[4], o[5], o[6], o[7]);
+            uint64_t *l = (uint64_t *)c->ctx.ws.get(Workspace::KMC_LUT, m.nlut * 8);
+            uint8_t *r = (uint8_t *)c->ctx.ws.get(Workspace::KMC_REC, m.record_bytes() + 1);
+            HIP_CHECK(hipMemcpyAsync(l, m.lut_bytes(), m.nlut * 8, hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(r, m.records(), m.record_bytes(), hipMemcpyHostToDevice, s));
+            dlut = l;
+            drec = r;
+        }
+        launch_kmc_decode(m, drec, dlut, dseq, seq_base, dstarts, dcounts, read_base, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));  // the slots are reused by the next database
+        seq_base += m.total * (m.k + 1) * (m.both ? 2 : 1);
+        read_base += m.total * (m.both ? 2 : 1);
+    }
+    split_fasta_files(c, dseq, &seq_base, per_read ? dstarts : nullptr, per_read ? dcounts : nullptr, &read_base,
+                      false);
+    HIP_CHECK(hipStreamSynchronize(s));
+    const double input_ms = ms_since(t_input);
+    return {BuildInput{dseq, seq_base, dstarts, dcounts, per_read ? total_reads : 0}, h2d_ms, input_ms};
+}
+
+// the build's rows -> the chunk: W / packed last / weights in pinned blocks the chunk owns
+static void fill_chunk(mtg_boss_ctor *c, const BuildOutput &o, mtg_boss_chunk *out) {
+    PinnedPool &pool = PinnedPool::get();
+    const uint64_t nwords = ceil_div(o.n, 64), last_bytes = std::max<uint64_t>(nwords, 1) * 8;
+    out->k = c->params.k;
+    out->alph_size = 5;
+    out->n = o.n;
+    out->bits_per_count = c->params.bits_per_count;
+    out->n_real = o.n_real;
+    out->n_dummy = o.n_dummy;
+    std::memcpy(out->F, o.F, sizeof(o.F));
+    if (o.host) {  // the spilled build: its rows are already on the host
+        out->W = (uint8_t *)pool.take(std::max<uint64_t>(o.n, 1));
+        std::memcpy(out->W, o.W, o.n);
+        out->last = (uint64_t *)pool.take(last_bytes);
+        std::memset(out->last, 0, last_bytes);
+        for (uint64_t i = 0; i < o.n; ++i) out->last[i >> 6] |= (uint64_t)(o.last[i] & 1) << (i & 63);
+        if (o.weights) {
+            out->weights = (uint32_t *)pool.take(std::max<uint64_t>(o.n, 1) * 4);
+            std::memcpy(out->weights, o.weights, o.n * 4);
         }
         return;
     }
-    for (uint64_t i = i0; i < n; ++i) {
-        out[bytes * i] = (uint8_t)w[i];
-        if (bytes == 2) out[2 * i + 1] = (uint8_t)(w[i] >> 8);
-    }
-}
-
-// weights[0..n) (u32) on the device -> the host's u32 array: for count widths <= 16 bits they cross
-// PCIe as 1 or 2 bytes a weight (configs[4]'s 8-bit weights: 1.5 GB -> 0.39 GB), in 16 MiB pieces
-// that the host threads widen as they land
-static void copy_weights_to_host(mtg_boss_ctor *c, const uint32_t *dwt, uint64_t n, unsigned bits, uint32_t *out) {
-    if (!n) return;
     hipStream_t s = c->ctx.stream;
-    const unsigned bytes = bits <= 8 ? 1 : bits <= 16 ? 2 : 4;
-    if (bytes == 4 || n < (16ull << 20)) {
-        HIP_CHECK(hipMemcpyAsync(out, dwt, n * 4, hipMemcpyDeviceToHost, s));
-        return;
+    uint64_t *dbits = (uint64_t *)c->ctx.ws.get(Workspace::LAST_BITS, last_bytes);
+    if (nwords) {
+        pack_bits_kernel<<<dim3((unsigned)ceil_div(nwords, 256)), dim3(256), 0, s>>>(o.last, o.n, dbits);
+        HIP_CHECK(hipGetLastError());
     }
-    const uint64_t nb = n * bytes;
-    uint8_t *dn = (uint8_t *)c->ctx.ws.get(Workspace::WN, nb + 64);
-    narrow_weights_kernel<<<dim3((unsigned)ceil_div(ceil_div(n, 16), 256)), dim3(256), 0, s>>>(dwt, n, bytes, dn);
-    HIP_CHECK(hipGetLastError());
-    if (c->wn_cap < nb + 64) {  // the ctor's pinned landing buffer, grown on demand
-        if (c->wn_host) (void)hipHostFree(c->wn_host);
-        c->wn_host = nullptr;
-        c->wn_cap = 0;
-        HIP_CHECK(hipHostMalloc((void **)&c->wn_host, nb + nb / 4 + 64, hipHostMallocDefault));
-        c->wn_cap = nb + nb / 4 + 64;
+    out->W = (uint8_t *)pool.take(o.n);
+    out->last = (uint64_t *)pool.take(last_bytes);
+    HIP_CHECK(hipMemcpyAsync(out->last, dbits, nwords * 8, hipMemcpyDeviceToHost, s));
+    copy_w_to_host(c->ctx, c->device, stage_threads(c), c->land_w4, o.W, o.n, out->W);
+    if (o.weights) {
+        out->weights = (uint32_t *)pool.take(o.n * 4);
+        copy_weights_to_host(c->ctx, c->device, stage_threads(c), c->land_wn, o.weights, o.n, c->params.bits_per_count,
+                             out->weights);
     }
-    uint8_t *hn = c->wn_host;
-    constexpr uint64_t PIECE = 16ull << 20;  // narrowed bytes per piece (a multiple of 2)
-    const uint64_t np = ceil_div(nb, PIECE);
-    std::vector<hipEvent_t> ev(np);
-    for (uint64_t p = 0; p < np; ++p) {
-        const uint64_t b0 = p * PIECE, len = std::min(PIECE, nb - b0);
-        HIP_CHECK(hipEventCreateWithFlags(&ev[p], hipEventDisableTiming));
-        HIP_CHECK(hipMemcpyAsync(hn + b0, dn + b0, len, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipEventRecord(ev[p], s));
-    }
-    const unsigned T = std::max(1u, std::min<unsigned>(stage_threads(c), (unsigned)np));
-    std::atomic<bool> failed{false};
-    parallel_ranges(T, T, 1, [&](uint64_t t0, uint64_t t1) {
-        DeviceGuard g(c->device);
-        for (uint64_t t = t0; t < t1; ++t)
-            for (uint64_t p = t; p < np; p += T) {
-                if (hipEventSynchronize(ev[p]) != hipSuccess) {
-                    failed = true;
-                    return;
-                }
-                const uint64_t b0 = p * PIECE, len = std::min(PIECE, nb - b0);
-                const uint64_t w0 = b0 / bytes, wn = len / bytes;
-                if (bytes == 1)
-                    for (uint64_t i = 0; i < wn; ++i) out[w0 + i] = hn[b0 + i];
-                else
-                    for (uint64_t i = 0; i < wn; ++i) out[w0 + i] = (uint32_t)hn[b0 + 2 * i] | (uint32_t)hn[b0 + 2 * i + 1] << 8;
-            }
-    });
-    for (auto e : ev) (void)hipEventDestroy(e);
-    if (failed) throw std::runtime_error("weights copy to the host failed");
+    HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// build_chunk on the staged reads: one H2D copy of the pinned read buffer (+ KMC records), the
-// device path, then W / packed last / weights D2H into pinned blocks the chunk owns
+// the batch is built: its timings, and the staged inputs dropped (under the build's exclusive stage lock: a
+// waiting add lands in the next batch)
+static void finish_batch(mtg_boss_ctor *c, std::unique_lock<std::shared_mutex> &stage_lock, const StagedInput &si,
+                         double d2h_ms, std::chrono::steady_clock::time_point t_start) {
+    mtg_boss_timings &T = c->ctx.timings;
+    T.d2h_ms = d2h_ms;
+    T.h2d_ms = si.h2d_ms;
+    T.input_ms = si.input_ms;
+    T.stage_ms = (double)c->stage_ns.exchange(0) * 1e-6;
+    c->stage.clear_locked();
+    stage_lock.unlock();
+    c->kmc.clear();
+    for (auto &f : c->fasta) free_fasta(f);
+    c->fasta.clear();
+    T.host_total_ms = ms_since(t_start);
+}
+
+// build_chunk on the staged reads: the inputs to the device, the device path, the rows to the host
 static int build_chunk_impl(mtg_boss_ctor *c, mtg::Comm *comm, mtg_boss_chunk *out) {
-    if (!c || !out) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (!c || !out) return bad_arguments();
     if (comm && !c->suffix.empty()) {
         set_error(kSuffixDist);
         return MTG_ERR_UNSUPPORTED;
@@ -3836,200 +3710,42 @@ static int build_chunk_impl(mtg_boss_ctor *c, mtg::Comm *comm, mtg_boss_chunk *o
     std::lock_guard<std::mutex> kmc_lock(c->kmc_mu);
     std::lock_guard<std::mutex> fa_lock(c->fa_mu);
     std::memset(out, 0, sizeof(*out));
-    try {
+    const int rc = abi_call(MTG_ERR_DEVICE, [&] {
         HIP_CHECK(hipSetDevice(c->device));
-        hipStream_t s = c->ctx.stream;
-        HostStage &st = c->stage;
-        const uint64_t len = st.size();
-        const uint64_t nr = st.n_reads();
-        uint64_t kmc_bytes = 0, kmc_reads = 0;
-        for (const auto &m : c->kmc) {
-            kmc_bytes += m.total * (m.k + 1) * (m.both ? 2 : 1);
-            kmc_reads += m.total * (m.both ? 2 : 1);
-        }
-        uint64_t fa_bytes = 0, fa_reads = 0;
-        for (const auto &f : c->fasta) fa_bytes += f.size + 1;  // split output <= raw bytes + a separator
-        const bool per_read_inputs = st.any_count_not_one() || kmc_reads;
-        if (c->params.bits_per_count && per_read_inputs && !c->fasta.empty()) {
-            uint64_t sb = 0;  // record counts first: the read-start arrays are sized by them
-            split_fasta_files(c, nullptr, &sb, nullptr, nullptr, &fa_reads, true);
-        }
-        const uint64_t total_len = len + kmc_bytes + fa_bytes, total_reads = nr + kmc_reads + fa_reads;
-        const auto t_h2d = std::chrono::steady_clock::now();
-        uint8_t *dseq = (uint8_t *)c->ctx.ws.get(Workspace::SEQ, total_len + 1);
-        if (len) {
-            // the staged 2-bit codes + valid mask: on the device already (the stage's mirror, copied
-            // while the reads were staged), else copied now; unpacked to one byte per char
-            const uint64_t nw = len / 32;
-            const uint64_t *dcodes = nullptr;
-            const uint32_t *dvalid = nullptr;
-            if (!st.mirror_wait(&dcodes, &dvalid)) {
-                uint64_t *pk = (uint64_t *)c->ctx.ws.get(Workspace::PACKED, nw * 12);
-                HIP_CHECK(hipMemcpyAsync(pk, st.codes(), nw * 8, hipMemcpyHostToDevice, s));
-                HIP_CHECK(hipMemcpyAsync(pk + nw, st.valid(), nw * 4, hipMemcpyHostToDevice, s));
-                dcodes = pk;
-                dvalid = (const uint32_t *)(pk + nw);
-            }
-            unpack_reads_kernel<<<dim3((unsigned)ceil_div(nw, 256)), dim3(256), 0, s>>>(dcodes, dvalid, nw, dseq);
-            HIP_CHECK(hipGetLastError());
-        }
-        uint64_t *dstarts = nullptr;
-        uint32_t *dcounts = nullptr;
-        const bool per_read = c->params.bits_per_count && per_read_inputs && total_reads;
-        if (per_read) {
-            dstarts = (uint64_t *)c->ctx.ws.get(Workspace::STARTS, total_reads * 8);
-            dcounts = (uint32_t *)c->ctx.ws.get(Workspace::RCOUNTS, total_reads * 4);
-            if (nr) {
-                HIP_CHECK(hipMemcpyAsync(dstarts, st.starts().data(), nr * 8, hipMemcpyHostToDevice, s));
-                HIP_CHECK(hipMemcpyAsync(dcounts, st.counts().data(), nr * 4, hipMemcpyHostToDevice, s));
-            }
-        }
-        HIP_CHECK(hipStreamSynchronize(s));
-        const double h2d_ms = ms_since(t_h2d);
-        // KMC records -> reads, on the device (kmc.hpp)
-        const auto t_input = std::chrono::steady_clock::now();
-        uint64_t seq_base = len, read_base = nr;
-        for (const auto &m : c->kmc) {
-            const uint64_t *dlut;
-            const uint8_t *drec;
-            if (m.dpre) {  // copied while add_kmc read the files (same stream)
-                dlut = (const uint64_t *)(m.dpre + 8);
-                drec = m.dsuf + 8;
-            } else {
-                uint64_t *l = (uint64_t *)c->ctx.ws.get(Workspace::KMC_LUT, m.nlut * 8);
-                uint8_t *r = (uint8_t *)c->ctx.ws.get(Workspace::KMC_REC, m.record_bytes() + 1);
-                HIP_CHECK(hipMemcpyAsync(l, m.lut_bytes(), m.nlut * 8, hipMemcpyHostToDevice, s));
-                HIP_CHECK(hipMemcpyAsync(r, m.records(), m.record_bytes(), hipMemcpyHostToDevice, s));
-                dlut = l;
-                drec = r;
-            }
-            kmc_decode_kernel<<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(m.total, 256), 65536))),
-                                dim3(256), 0, s>>>(drec, dlut, m.nlut, m.total, m.k, m.lut_len,
-                                                   m.counter_size, m.min_count, m.max_count, m.both ? 1 : 0,
-                                                   dseq, seq_base, dstarts, dcounts, read_base);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipStreamSynchronize(s));  // the slots are reused by the next database
-            seq_base += m.total * (m.k + 1) * (m.both ? 2 : 1);
-            read_base += m.total * (m.both ? 2 : 1);
-        }
-        split_fasta_files(c, dseq, &seq_base, per_read ? dstarts : nullptr, per_read ? dcounts : nullptr, &read_base,
-                          false);
-        HIP_CHECK(hipStreamSynchronize(s));
-        const double input_ms = ms_since(t_input);
-        BuildInput in{dseq, seq_base, dstarts, dcounts, per_read ? total_reads : 0};
+        const StagedInput si = stage_inputs(c);
         BuildOutput o{};
-        c->ctx.host_output = comm == nullptr;  // a single build with host arrays may spill
-        dispatch_build(c, comm, in, &o);
-        c->ctx.host_output = false;
+        dispatch_build(c, comm, si.in, comm == nullptr, &o);  // a single build with host arrays may spill
         const auto t_d2h = std::chrono::steady_clock::now();
-        if (o.host) {  // the spilled build: its rows are already on the host
-            PinnedPool &pool = PinnedPool::get();
-            const uint64_t nwords = ceil_div(o.n, 64);
-            out->k = c->params.k;
-            out->alph_size = 5;
-            out->n = o.n;
-            out->bits_per_count = c->params.bits_per_count;
-            out->n_real = o.n_real;
-            out->n_dummy = o.n_dummy;
-            std::memcpy(out->F, o.F, sizeof(o.F));
-            out->W = (uint8_t *)pool.take(std::max<uint64_t>(o.n, 1));
-            std::memcpy(out->W, o.W, o.n);
-            out->last = (uint64_t *)pool.take(std::max<uint64_t>(nwords, 1) * 8);
-            std::memset(out->last, 0, std::max<uint64_t>(nwords, 1) * 8);
-            for (uint64_t i = 0; i < o.n; ++i) out->last[i >> 6] |= (uint64_t)(o.last[i] & 1) << (i & 63);
-            if (o.weights) {
-                out->weights = (uint32_t *)pool.take(std::max<uint64_t>(o.n, 1) * 4);
-                std::memcpy(out->weights, o.weights, o.n * 4);
-            }
-            c->ctx.spill_W = std::vector<uint8_t>();
-            c->ctx.spill_last = std::vector<uint8_t>();
-            c->ctx.spill_weights = std::vector<uint32_t>();
-            mtg_boss_timings &T = c->ctx.timings;
-            T.d2h_ms = ms_since(t_d2h);
-            T.h2d_ms = h2d_ms;
-            T.input_ms = input_ms;
-            T.stage_ms = (double)c->stage_ns.exchange(0) * 1e-6;
-            c->stage.clear_locked();
-            stage_lock.unlock();
-            c->kmc.clear();
-            for (auto &f : c->fasta) free_fasta(f);
-            c->fasta.clear();
-            T.host_total_ms = ms_since(t_start);
-            return MTG_OK;
-        }
-        const uint64_t nwords = ceil_div(o.n, 64);
-        uint64_t *dbits = (uint64_t *)c->ctx.ws.get(Workspace::LAST_BITS, std::max<uint64_t>(nwords, 1) * 8);
-        if (nwords) {
-            pack_bits_kernel<<<dim3((unsigned)ceil_div(nwords, 256)), dim3(256), 0, s>>>(o.last, o.n, dbits);
-            HIP_CHECK(hipGetLastError());
-        }
-        out->k = c->params.k;
-        out->alph_size = 5;
-        out->n = o.n;
-        out->bits_per_count = c->params.bits_per_count;
-        out->n_real = o.n_real;
-        out->n_dummy = o.n_dummy;
-        std::memcpy(out->F, o.F, sizeof(o.F));
-        PinnedPool &pool = PinnedPool::get();
-        out->W = (uint8_t *)pool.take(o.n);
-        out->last = (uint64_t *)pool.take(std::max<uint64_t>(nwords, 1) * 8);
-        HIP_CHECK(hipMemcpyAsync(out->last, dbits, nwords * 8, hipMemcpyDeviceToHost, s));
-        copy_w_to_host(c, o.W, o.n, out->W);
-        if (o.weights) {
-            out->weights = (uint32_t *)pool.take(o.n * 4);
-            copy_weights_to_host(c, o.weights, o.n, c->params.bits_per_count, out->weights);
-        }
-        HIP_CHECK(hipStreamSynchronize(s));
-        mtg_boss_timings &T = c->ctx.timings;
-        T.d2h_ms = ms_since(t_d2h);
-        T.h2d_ms = h2d_ms;
-        T.input_ms = input_ms;
-        T.stage_ms = (double)c->stage_ns.exchange(0) * 1e-6;
-        c->stage.clear_locked();  // under the build's exclusive lock: a waiting add lands in the next batch
-        stage_lock.unlock();
-        c->kmc.clear();
-        for (auto &f : c->fasta) free_fasta(f);
-        c->fasta.clear();
-        T.host_total_ms = ms_since(t_start);
+        fill_chunk(c, o, out);
+        finish_batch(c, stage_lock, si, ms_since(t_d2h), t_start);
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        mtg_boss_chunk_free(out);
-        return MTG_ERR_DEVICE;
-    }
+    });
+    if (rc != MTG_OK) mtg_boss_chunk_free(out);
+    return rc;
 }
 
 int mtg_kmc_write_device(mtg_boss_ctor *c, const uint8_t *d_seq, uint64_t seq_len, unsigned k, int canonical,
                          unsigned counter_size, unsigned lut_len, const char *outbase, uint64_t *n_written) {
-    if (!c || !outbase || (seq_len && !d_seq)) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (!c || !outbase || (seq_len && !d_seq)) return bad_arguments();
     std::lock_guard<std::mutex> lock(c->mu);
-    try {
+    return abi_call(MTG_ERR_DEVICE, [&] {
         HIP_CHECK(hipSetDevice(c->device));
         BuildInput in{d_seq, seq_len, nullptr, nullptr, 0};
         const uint64_t n = mtg::kmc_count_write(c->ctx, in, k, canonical != 0, counter_size, lut_len, outbase,
                                                 stage_threads(c));
         if (n_written) *n_written = n;
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_DEVICE;
-    }
+    });
 }
 
 int mtg_kmc_load_device(const char *kmc_path, uint64_t min_count, uint64_t max_count, int call_both_from_canonical,
                         int device_id, mtg_device_reads *out) {
-    if (!kmc_path || !out) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (!kmc_path || !out) return bad_arguments();
     std::memset(out, 0, sizeof(*out));
     out->device_id = device_id;
     uint64_t *dlut = nullptr;
     uint8_t *drec = nullptr;
-    try {
+    const int rc = abi_call(MTG_ERR_DEVICE, [&] {
         KmcInput m = kmc_open(kmc_path, min_count, max_count, call_both_from_canonical != 0);
         HIP_CHECK(hipSetDevice(device_id));
         const uint64_t per = m.both ? 2 : 1;
@@ -4043,23 +3759,20 @@ int mtg_kmc_load_device(const char *kmc_path, uint64_t min_count, uint64_t max_c
             HIP_CHECK(hipMalloc(&drec, m.record_bytes() + 1));
             HIP_CHECK(hipMemcpy(dlut, m.lut_bytes(), m.nlut * 8, hipMemcpyHostToDevice));
             HIP_CHECK(hipMemcpy(drec, m.records(), m.record_bytes(), hipMemcpyHostToDevice));
-            kmc_decode_kernel<<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(m.total, 256), 65536))),
-                                dim3(256)>>>(drec, dlut, m.nlut, m.total, m.k, m.lut_len, m.counter_size,
-                                             m.min_count, m.max_count, m.both ? 1 : 0, out->seq, 0, out->read_starts,
-                                             out->counts, 0);
+            launch_kmc_decode(m, drec, dlut, out->seq, 0, out->read_starts, out->counts, 0, nullptr);
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipDeviceSynchronize());
             (void)hipFree(dlut);
             (void)hipFree(drec);
         }
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
+    });
+    if (rc != MTG_OK) {
         if (dlut) (void)hipFree(dlut);
         if (drec) (void)hipFree(drec);
         mtg_device_reads_free(out);
-        return MTG_ERR_DEVICE;
     }
+    return rc;
 }
 
 void mtg_device_reads_free(mtg_device_reads *r) {
@@ -4090,15 +3803,12 @@ struct mtg_comm {
 
 int mtg_comm_get_unique_id(uint8_t *id) {
     if (!id) return MTG_ERR_ARGUMENT;
-    try {
+    return abi_call(MTG_ERR_DEVICE, [&] {
         ncclUniqueId u;
         RCCL_CHECK(RcclApi::get().GetUniqueId(&u));
         std::memcpy(id, u.internal, MTG_COMM_ID_BYTES);
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_DEVICE;
-    }
+    });
 }
 
 mtg_comm *mtg_comm_create_rccl(const uint8_t *id, int world, int rank, int device_id) {
@@ -4119,10 +3829,7 @@ mtg_comm *mtg_comm_create_rccl(const uint8_t *id, int world, int rank, int devic
 }
 
 int mtg_comm_create_local(int world, mtg_comm **comms) {
-    if (world < 1 || world > mtg::MAX_RANKS || !comms) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (world < 1 || world > mtg::MAX_RANKS || !comms) return bad_arguments();
     auto group = std::make_shared<mtg::LocalGroup>(world);
     const char *ser = getenv("MTG_LOCAL_SERIAL");
     group->serial = ser && ser[0] == '1';
@@ -4163,19 +3870,13 @@ int mtg_comm_size(const mtg_comm *comm) { return comm ? comm->comm->size() : -1;
 int mtg_boss_build_device_dist(mtg_boss_ctor *c, mtg_comm *comm, const uint8_t *d_seq, uint64_t seq_len,
                                const uint64_t *d_read_starts, const uint32_t *d_counts, uint64_t n_reads,
                                void *stream, mtg_boss_device_chunk *out) {
-    if (!comm) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (!comm) return bad_arguments();
     return build_device_impl(c, comm->comm.get(), d_seq, seq_len, d_read_starts, d_counts, n_reads, stream,
                              out);
 }
 
 int mtg_boss_ctor_build_chunk_dist(mtg_boss_ctor *c, mtg_comm *comm, mtg_boss_chunk *out) {
-    if (!comm) {
-        set_error("bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+    if (!comm) return bad_arguments();
     return build_chunk_impl(c, comm->comm.get(), out);
 }
 
@@ -4208,397 +3909,46 @@ void mtg_boss_chunk_free(mtg_boss_chunk *chunk) {
 
 int mtg_boss_write_dbg(const mtg_boss_chunk *chunk, const char *outbase, int graph_mode, int mask_dummy,
                        int64_t suffix_length, uint64_t *n_valid) {
-    if (!chunk || !outbase || !chunk->W || !chunk->last || chunk->n < 1 || graph_mode < 0 || graph_mode > 1) {
-        set_error("write_dbg: bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
-    try {
+    if (!chunk || !outbase || !chunk->W || !chunk->last || chunk->n < 1 || graph_mode < 0 || graph_mode > 1)
+        return bad_arguments("write_dbg: bad arguments");
+    return abi_call(MTG_ERR_ARGUMENT, [&] {
         const uint64_t v = dbgio::write_dbg(outbase, chunk->W, chunk->last, chunk->n, chunk->F, chunk->k,
                                             (uint64_t)graph_mode, mask_dummy, suffix_length, chunk->weights,
                                             chunk->bits_per_count);
         if (n_valid) *n_valid = v;
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_ARGUMENT;
-    }
+    });
 }
-
-}  // extern "C"
-
-// ---- the graph files from a device chunk: the kernels of dbg_device.hpp compute the payload of
-// dbg_io.hpp's write_dbg_payload, the host keeps the Huffman shape, the select supports,
-// bit_vector_small and the framing
-namespace {
-
-struct DbgArgumentError : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-
-// device scratch of one call: hipMalloc'ed, regrown on demand, freed when the call returns
-struct DevScratch {
-    struct Buf {
-        void *p = nullptr;
-        uint64_t cap = 0;
-    };
-    std::vector<Buf *> all;
-    ~DevScratch() {
-        for (Buf *b : all) {
-            if (b->p) (void)hipFree(b->p);  // waits for the device
-            delete b;
-        }
-    }
-    Buf *make() {
-        all.push_back(new Buf());
-        return all.back();
-    }
-    template <typename T>
-    static T *ensure(Buf *b, uint64_t count) {
-        const uint64_t bytes = std::max<uint64_t>(count * sizeof(T), 256);
-        if (b->cap < bytes) {
-            if (b->p) HIP_CHECK(hipFree(b->p));
-            b->p = nullptr;
-            b->cap = 0;
-            HIP_CHECK(hipMalloc(&b->p, bytes));
-            b->cap = bytes;
-        }
-        return (T *)b->p;
-    }
-    template <typename T>
-    T *take(uint64_t count) { return ensure<T>(make(), count); }
-};
-
-struct PinnedBlocks {
-    std::vector<void *> all;
-    ~PinnedBlocks() {
-        for (void *p : all) (void)PinnedPool::get().give(p);
-    }
-    template <typename T>
-    T *take(uint64_t count) {
-        all.push_back(PinnedPool::get().take(std::max<uint64_t>(count, 1) * sizeof(T)));
-        return (T *)all.back();
-    }
-};
-
-unsigned dbg_grid(uint64_t items) {
-    const uint64_t g = ceil_div(std::max<uint64_t>(items, 1), dbgdev::kThreads);
-    if (g > 0x7FFFFFFFull) throw std::runtime_error("write_dbg_device: too many rows for one launch");
-    return (unsigned)g;
-}
-
-uint64_t write_dbg_device_impl(Ctx &ctx, const mtg_boss_device_chunk &ch, unsigned bits_per_count,
-                               const std::string &base, uint64_t mode, int mask_dummy, int64_t suffix_length,
-                               mtg_dbg_write_timings *T) {
-    using namespace dbgdev;
-    hipStream_t s = ctx.stream;
-    const uint64_t n = ch.n, nw = ceil_div(n, 64), k = ch.k;
-    const uint64_t L = dbgio::indexed_suffix_length(suffix_length, k);
-    if (L > 13) throw std::runtime_error("write_dbg_device: a suffix index of 4^" + std::to_string(L) +
-                                         " ranges does not fit the device writer");
-    const bool navigate = mask_dummy || L;
-    const bool weighted = ch.weights && bits_per_count;
-    PinnedBlocks pin;  // given back after the device scratch is freed (hipFree waits for the copies)
-    DevScratch dev;
-    hipEvent_t ev[2];
-    for (auto &e : ev) HIP_CHECK(hipEventCreate(&e));
-    struct EvGuard {
-        hipEvent_t *ev;
-        ~EvGuard() {
-            for (int i = 0; i < 2; ++i) (void)hipEventDestroy(ev[i]);
-        }
-    } ev_guard{ev};
-    HIP_CHECK(hipEventRecord(ev[0], s));
-
-    enum { S_HIST = 0, S_NAV = 18, S_NVALID = 24, S_ONES = 25, S_COUNT = 26, S_WORDS = 32 };
-    uint64_t *d_small = dev.take<uint64_t>(S_WORDS);
-    uint64_t *h_small = pin.take<uint64_t>(S_WORDS);
-    HIP_CHECK(hipMemsetAsync(d_small, 0, S_WORDS * 8, s));
-
-    // 1. W histogram per tile, its scan, the shape (host)
-    const uint64_t ntiles = ceil_div(n, kTile), nh = 17 * ntiles;
-    if (ntiles > 0x7FFFFFFFull) throw std::runtime_error("write_dbg_device: too many rows for one launch");
-    uint32_t *hist = dev.take<uint32_t>(nh);
-    uint64_t *hscan = dev.take<uint64_t>(nh + 1);
-    DevScratch::Buf *scan_tmp_buf = dev.make();
-    auto scan_tmp = [&](uint64_t items) { return DevScratch::ensure<uint64_t>(scan_tmp_buf, ceil_div(items, kScanTile) + 1); };
-    w_hist_kernel<<<dim3((unsigned)ntiles), dim3(kThreads), 0, s>>>(ch.W, n, ntiles, hist);
-    HIP_CHECK(hipGetLastError());
-    exclusive_scan(hist, nh, hscan, scan_tmp(nh), s);
-    {
-        GatherIdx g{};
-        for (int i = 0; i < 18; ++i) g.idx[i] = (uint64_t)i * ntiles;
-        gather_kernel<<<dim3(1), dim3(64), 0, s>>>(hscan, g, 18, d_small + S_HIST);
-        HIP_CHECK(hipGetLastError());
-    }
-    HIP_CHECK(hipMemcpyAsync(h_small, d_small, 18 * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (h_small[17] != h_small[16])
-        throw DbgArgumentError("write_dbg_device: W holds " + std::to_string(h_small[17] - h_small[16]) +
-                               " values above 15 (a BOSS label is a 4-bit code)");
-    dbgio::DbgPayload P;
-    P.n = n;
-    P.L = L;
-    sdslio::WtHuffPayload &wt = P.wt;
-    uint64_t freq[256] = {0};
-    WtTable tb{};
-    for (int c = 0; c < 16; ++c) {
-        freq[c] = h_small[c + 1] - h_small[c];
-        tb.row_base[c] = h_small[c];
-        wt.sigma += freq[c] != 0;
-    }
-    wt.n = n;
-    wt.tree = sdslio::huff_shape(freq);
-    wt.total = sdslio::huff_total_bits(wt.tree);
-    std::vector<int> inner_of(wt.tree.nodes.size(), -1);
-    for (size_t v = 0; v < wt.tree.nodes.size(); ++v)
-        if (wt.tree.nodes[v].child[0] != 0xFFFF) {
-            if (tb.ninner >= (uint32_t)kMaxInner) throw std::runtime_error("write_dbg_device: bad Huffman shape");
-            inner_of[v] = (int)tb.ninner;
-            tb.bv_pos[tb.ninner++] = wt.tree.nodes[v].bv_pos;
-        }
-    for (int c = 0; c < 16; ++c) {
-        if (wt.tree.leaf[c] == 0xFFFF) continue;
-        const uint64_t path = wt.tree.path[c], len = path >> 56;
-        uint16_t v = 0;
-        for (uint64_t d = 0; d < len; ++d) {
-            const uint64_t b = (path >> d) & 1;
-            tb.under[inner_of[v]] |= (uint16_t)(1u << c);
-            if (b) tb.one[inner_of[v]] |= (uint16_t)(1u << c);
-            v = wt.tree.nodes[v].child[b];
-        }
-    }
-
-    // 2. the node bits; 4. their rank_support_v<1> words
-    const uint64_t bvw = ceil_div(wt.total, 64);
-    uint64_t *bv = dev.take<uint64_t>(bvw);
-    HIP_CHECK(hipMemsetAsync(bv, 0, std::max<uint64_t>(bvw, 1) * 8, s));
-    if (tb.ninner) {
-        wt_fill_kernel<<<dim3((unsigned)ntiles), dim3(kThreads), 0, s>>>(ch.W, n, ntiles, hscan, tb, bv, bvw);
-        HIP_CHECK(hipGetLastError());
-    }
-    const uint64_t nb_v = (bvw >> 3) + 1;
-    uint64_t *rank_v = dev.take<uint64_t>(2 * nb_v);
-    {
-        uint32_t *cnt = dev.take<uint32_t>(nb_v);
-        uint64_t *sc = dev.take<uint64_t>(nb_v + 1);
-        rank_blocks_kernel<8><<<dim3(dbg_grid(nb_v)), dim3(kThreads), 0, s>>>(bv, bvw, nb_v, cnt, rank_v);
-        HIP_CHECK(hipGetLastError());
-        exclusive_scan(cnt, nb_v, sc, scan_tmp(nb_v), s);
-        rank_first_kernel<<<dim3(dbg_grid(nb_v)), dim3(kThreads), 0, s>>>(sc, nb_v, rank_v);
-        HIP_CHECK(hipGetLastError());
-    }
-
-    // 3. last packed; 4. its rank_support_v5<1> words and its ones
-    uint64_t *lastw = dev.take<uint64_t>(nw);
-    pack_bits_kernel<<<dim3(dbg_grid(nw)), dim3(256), 0, s>>>(ch.last, n, lastw);
-    HIP_CHECK(hipGetLastError());
-    const uint64_t nb_5 = (nw >> 5) + 1;
-    uint64_t *rank_5 = dev.take<uint64_t>(2 * nb_5);
-    {
-        uint32_t *cnt = dev.take<uint32_t>(nb_5);
-        uint64_t *sc = dev.take<uint64_t>(nb_5 + 1);
-        rank_blocks_kernel<32><<<dim3(dbg_grid(nb_5)), dim3(kThreads), 0, s>>>(lastw, nw, nb_5, cnt, rank_5);
-        HIP_CHECK(hipGetLastError());
-        exclusive_scan(cnt, nb_5, sc, scan_tmp(nb_5), s);
-        rank_first_kernel<<<dim3(dbg_grid(nb_5)), dim3(kThreads), 0, s>>>(sc, nb_5, rank_5);
-        HIP_CHECK(hipGetLastError());
-        GatherIdx g{};
-        g.idx[0] = nb_5;
-        gather_kernel<<<dim3(1), dim3(64), 0, s>>>(sc, g, 1, d_small + S_ONES);
-        HIP_CHECK(hipGetLastError());
-    }
-
-    // 5. the navigation directory
-    Nav nav{};
-    if (navigate) {
-        uint32_t *cnt = dev.take<uint32_t>(6 * nw);
-        uint64_t *sc = dev.take<uint64_t>(6 * nw + 1);
-        uint64_t *dir = dev.take<uint64_t>(6 * (nw + 1));
-        nav_count_kernel<<<dim3(dbg_grid(nw)), dim3(kThreads), 0, s>>>(ch.W, lastw, n, nw, cnt);
-        HIP_CHECK(hipGetLastError());
-        exclusive_scan(cnt, 6 * nw, sc, scan_tmp(6 * nw), s);
-        nav_dir_kernel<<<dim3(dbg_grid(nw + 1), 6), dim3(kThreads), 0, s>>>(sc, nw, dir);
-        HIP_CHECK(hipGetLastError());
-        nav.W = ch.W;
-        nav.last = lastw;
-        nav.n = n;
-        nav.k = k;
-        nav.nw = nw;
-        nav.last_rank = dir;
-        for (int c = 0; c < 5; ++c) nav.wrank[c] = dir + (uint64_t)(1 + c) * (nw + 1);
-        FVec f{};
-        for (int c = 0; c < 5; ++c) f.F[c] = ch.F[c];
-        nav_nf_kernel<<<dim3(1), dim3(64), 0, s>>>(nav, f, d_small + S_NAV);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(h_small + S_NAV, d_small + S_NAV, 6 * 8, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        for (int c = 0; c < 5; ++c) nav.NF[c] = h_small[S_NAV + c];
-    }
-
-    // 6. the suffix-range index, one level per char
-    uint64_t n_ranges = 0;
-    uint64_t *ranges = nullptr;
-    if (L) {
-        n_ranges = 1ull << (2 * L);
-        uint64_t *a = dev.take<uint64_t>(2 * n_ranges), *b = dev.take<uint64_t>(2 * n_ranges);
-        suffix_root_kernel<<<dim3(1), dim3(64), 0, s>>>(n, a);
-        HIP_CHECK(hipGetLastError());
-        uint64_t num = 1;
-        for (uint64_t len = 1; len <= L; ++len, num *= 4) {
-            suffix_level_kernel<<<dim3(dbg_grid(4 * num)), dim3(kThreads), 0, s>>>(nav, a, num, b);
-            HIP_CHECK(hipGetLastError());
-            std::swap(a, b);
-        }
-        ranges = a;
-    }
-
-    // 7. the valid-edge mask
-    uint64_t *maskw = nullptr;
-    if (mask_dummy) {
-        uint8_t *flagged = dev.take<uint8_t>(n);
-        HIP_CHECK(hipMemsetAsync(flagged, 0, n, s));
-        if (n > 1) {
-            DevScratch::Buf *fb[2] = {dev.make(), dev.make()}, *cb = dev.make(), *sb = dev.make();
-            uint64_t *cur = DevScratch::ensure<uint64_t>(fb[0], 1);
-            HIP_CHECK(hipMemcpyAsync(cur, d_small + S_NAV + 5, 8, hipMemcpyDeviceToDevice, s));
-            uint64_t m = 1;
-            for (uint64_t depth = 0; depth < k && m; ++depth) {
-                const bool expand = depth + 1 < k;
-                uint32_t *cnt = DevScratch::ensure<uint32_t>(cb, m);
-                mask_count_kernel<<<dim3(dbg_grid(m)), dim3(kThreads), 0, s>>>(nav, cur, m, expand ? 1 : 0, cnt, flagged);
-                HIP_CHECK(hipGetLastError());
-                if (!expand) break;
-                uint64_t *sc = DevScratch::ensure<uint64_t>(sb, m + 1);
-                exclusive_scan(cnt, m, sc, scan_tmp(m), s);
-                HIP_CHECK(hipMemcpyAsync(h_small + S_COUNT, sc + m, 8, hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                const uint64_t next_m = h_small[S_COUNT];
-                if (next_m > n) throw DbgArgumentError("write_dbg_device: the arrays are no BOSS table (the source-dummy tree outgrows the rows)");
-                if (!next_m) break;
-                uint64_t *next = DevScratch::ensure<uint64_t>(fb[(depth + 1) & 1], next_m);
-                mask_expand_kernel<<<dim3(dbg_grid(m)), dim3(kThreads), 0, s>>>(nav, cur, m, sc, next, next_m);
-                HIP_CHECK(hipGetLastError());
-                cur = next;
-                m = next_m;
-            }
-        }
-        maskw = dev.take<uint64_t>(nw);
-        mask_pack_kernel<<<dim3(dbg_grid(nw)), dim3(kThreads), 0, s>>>(ch.W, flagged, n, nw, maskw,
-                                                                    (unsigned long long *)(d_small + S_NVALID));
-        HIP_CHECK(hipGetLastError());
-    }
-
-    // 8. the weights' int_vector words
-    const uint64_t nww = weighted ? ceil_div(n * bits_per_count, 64) : 0;
-    uint64_t *wwords = nullptr;
-    if (weighted) {
-        wwords = dev.take<uint64_t>(nww);
-        weights_pack_kernel<<<dim3(dbg_grid(nww)), dim3(kThreads), 0, s>>>(ch.weights, n, bits_per_count, nww, wwords);
-        HIP_CHECK(hipGetLastError());
-    }
-    HIP_CHECK(hipEventRecord(ev[1], s));
-
-    // payloads -> pinned host blocks
-    HIP_CHECK(hipEventSynchronize(ev[1]));
-    const auto t_d2h = std::chrono::steady_clock::now();
-    uint64_t d2h_bytes = 0;
-    auto fetch = [&](const uint64_t *d, uint64_t words) {
-        uint64_t *h = pin.take<uint64_t>(words);
-        if (words) HIP_CHECK(hipMemcpyAsync(h, d, words * 8, hipMemcpyDeviceToHost, s));
-        d2h_bytes += words * 8;
-        return h;
-    };
-    uint64_t *h_bv = fetch(bv, bvw);
-    uint64_t *h_rank_v = fetch(rank_v, 2 * nb_v);
-    uint64_t *h_last = fetch(lastw, nw);
-    uint64_t *h_rank_5 = fetch(rank_5, 2 * nb_5);
-    uint64_t *h_ranges = L ? fetch(ranges, 2 * n_ranges) : nullptr;
-    uint64_t *h_mask = mask_dummy ? fetch(maskw, nw) : nullptr;
-    uint64_t *h_weights = weighted ? fetch(wwords, nww) : nullptr;
-    HIP_CHECK(hipMemcpyAsync(h_small + S_NVALID, d_small + S_NVALID, 2 * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    const double d2h_ms = ms_since(t_d2h);
-    float device_ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&device_ms, ev[0], ev[1]));
-
-    // host: the inner nodes' ranks from the rank words, the forward fill, the files
-    const auto t_host = std::chrono::steady_clock::now();
-    wt.bv = h_bv;
-    wt.rank = h_rank_v;
-    wt.rank_words = 2 * nb_v;
-    for (auto &v : wt.tree.nodes)
-        if (v.child[0] != 0xFFFF) v.bv_pos_rank = sdslio::rank_v_query(h_bv, h_rank_v, v.bv_pos);
-    P.last = h_last;
-    P.last_ones = h_small[S_ONES];
-    P.last_rank = h_rank_5;
-    P.last_rank_words = 2 * nb_5;
-    if (L) {
-        dbgio::fill_empty_ranges(h_ranges, n_ranges);
-        P.ranges = h_ranges;
-        P.n_ranges = n_ranges;
-    }
-    if (mask_dummy) {
-        P.valid = h_mask;
-        P.n_valid = h_small[S_NVALID];
-    }
-    if (weighted) {
-        P.weights = h_weights;
-        P.weight_width = bits_per_count;
-    }
-    double stage_ms[5] = {0, 0, 0, 0, 0};
-    const uint64_t n_valid = dbgio::write_dbg_payload(base, P, ch.F, k, mode, stage_ms);
-    if (ctx.knobs.trace)
-        fprintf(stderr, "[mtg trace] write_dbg_device host: wt_huff %.1f ms, last %.1f ms, index+framing %.1f ms, "
-                        "edgemask %.1f ms, weights %.1f ms\n",
-                stage_ms[0], stage_ms[1], stage_ms[2], stage_ms[3], stage_ms[4]);
-    if (T) {
-        T->device_ms = device_ms;
-        T->d2h_ms = d2h_ms;
-        T->host_ms = ms_since(t_host);
-        T->d2h_bytes = d2h_bytes;
-    }
-    return n_valid;
-}
-
-}  // namespace
-
-extern "C" {
 
 int mtg_boss_write_dbg_device(mtg_boss_ctor *c, const mtg_boss_device_chunk *chunk, uint8_t bits_per_count,
                               const char *outbase, int graph_mode, int mask_dummy, int64_t suffix_length,
                               uint64_t *n_valid, mtg_dbg_write_timings *timings) {
     if (!c || !chunk || !outbase || !chunk->W || !chunk->last || chunk->n < 1 || graph_mode < 0 || graph_mode > 1 ||
-        mask_dummy < 0 || mask_dummy > 2 || bits_per_count > 32) {
-        set_error("write_dbg_device: bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
+        mask_dummy < 0 || mask_dummy > 2 || bits_per_count > 32)
+        return bad_arguments("write_dbg_device: bad arguments");
     if (mask_dummy == 2) {
         set_error("write_dbg_device: pruning (mask_dummy = 2) runs in the host writer only: copy the chunk to the "
                   "host and call mtg_boss_write_dbg");
         return MTG_ERR_UNSUPPORTED;
     }
     std::lock_guard<std::mutex> lock(c->mu);
-    try {
-        HIP_CHECK(hipSetDevice(c->device));
-        const uint64_t v = write_dbg_device_impl(c->ctx, *chunk, bits_per_count, outbase, (uint64_t)graph_mode,
-                                                 mask_dummy, suffix_length, timings);
-        if (n_valid) *n_valid = v;
-        return MTG_OK;
-    } catch (const DbgArgumentError &e) {
-        set_error(e.what());
-        return MTG_ERR_ARGUMENT;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_DEVICE;
-    }
+    return abi_call(MTG_ERR_DEVICE, [&] {
+        try {
+            HIP_CHECK(hipSetDevice(c->device));
+            const uint64_t v = write_dbg_device_impl(c->ctx, *chunk, bits_per_count, outbase, (uint64_t)graph_mode,
+                                                     mask_dummy, suffix_length, timings);
+            if (n_valid) *n_valid = v;
+            return MTG_OK;
+        } catch (const DbgArgumentError &e) {  // the caller's arrays are no BOSS table
+            set_error(e.what());
+            return MTG_ERR_ARGUMENT;
+        }
+    });
 }
 
 int mtg_sdsl_write(const char *path, int kind, const void *data, uint64_t nbits) {
-    if (!path || (!data && nbits) || kind < 0 || kind > 4) {
-        set_error("sdsl_write: bad arguments");
-        return MTG_ERR_ARGUMENT;
-    }
-    try {
+    if (!path || (!data && nbits) || kind < 0 || kind > 4) return bad_arguments("sdsl_write: bad arguments");
+    return abi_call(MTG_ERR_ARGUMENT, [&] {
         std::ofstream o(path, std::ios::binary);
         if (!o.good()) throw std::runtime_error(std::string("Can't write to file ") + path);
         const uint64_t *w = (const uint64_t *)data;
@@ -4617,16 +3967,13 @@ int mtg_sdsl_write(const char *path, int kind, const void *data, uint64_t nbits)
         }
         if (!o.good()) throw std::runtime_error(std::string("Can't write to file ") + path);
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return MTG_ERR_ARGUMENT;
-    }
+    });
 }
 
 int mtg_boss_read_dbg(const char *outbase, mtg_dbg_file *out) {
     if (!outbase || !out) return MTG_ERR_ARGUMENT;
     std::memset(out, 0, sizeof(*out));
-    try {
+    const int rc = abi_call(MTG_ERR_ARGUMENT, [&] {
         dbgio::DbgFile f = dbgio::read_dbg(outbase);
         out->k = f.k;
         out->n = f.n;
@@ -4650,11 +3997,9 @@ int mtg_boss_read_dbg(const char *outbase, mtg_dbg_file *out) {
             for (uint64_t x : f.valid) out->n_valid += __builtin_popcountll(x);
         }
         return MTG_OK;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        mtg_dbg_file_free(out);
-        return MTG_ERR_ARGUMENT;
-    }
+    });
+    if (rc != MTG_OK) mtg_dbg_file_free(out);
+    return rc;
 }
 
 void mtg_dbg_file_free(mtg_dbg_file *f) {
@@ -4701,18 +4046,6 @@ int mtg_memcpy_h2d(void *dst, const void *src, uint64_t bytes) {
 
 int mtg_memcpy_d2h(void *dst, const void *src, uint64_t bytes) {
     return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? MTG_OK : MTG_ERR_DEVICE;
-}
-
-// The bench's achievable-bandwidth copy: one 16-byte nontemporal vector load and store per thread
-// (global_load_dwordx4 / global_store_dwordx4 nt), a workgroup per 4 KiB.  tools/copy_bench.hip on
-// MI355X, 4 GiB (profiles/r6_copy_bench.txt): 6.44 TB/s -- above the guide's 6.29 float4 copy -- against
-// 6.21 for plain 16-byte accesses, 5.85 for round 5's 4 x (2 x 8-byte nt) per thread (the kernel this
-// replaces: its 8-byte nt halves), 4.6-4.95 for grid-stride loops, 4.96 for hipMemcpyAsync D2D.
-typedef unsigned int mtg_u32x4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void copy16_kernel(const mtg_u32x4 *__restrict__ src, mtg_u32x4 *__restrict__ dst,
-                                                     uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);
 }
 
 int mtg_device_copy(void *dst, const void *src, uint64_t bytes, void *stream) {

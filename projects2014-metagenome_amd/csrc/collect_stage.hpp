@@ -15,7 +15,13 @@ struct BuildInput {
     const uint32_t *read_counts;
     uint64_t n_reads;
     const uint64_t *rid_at = nullptr;  // per-read counts: the read of every 4 K-position block
+    int canon_mode = 1;                // the canonical representative the extraction keeps (cmode)
 };
+
+// the extraction kernels' canonical argument: 0 basic, 1 min(fwd, rc), 2 the strand whose top 12 bits hash
+// smaller (boss_kernels.hpp: take_rc) -- any one representative per {x, rc x} gives the same real edges and
+// weights; 2 spreads the representatives over the key space (the super-k-mer owners of a multi-GPU build)
+static inline int cmode(const BuildInput &in, bool canonical) { return canonical ? in.canon_mode : 0; }
 
 // window positions of the read buffer (valid or not)
 static uint64_t n_windows(const BuildInput &in, unsigned K) { return in.seq_len >= K ? in.seq_len - K + 1 : 0; }

@@ -335,6 +335,10 @@ struct Knobs {
     bool force_spill = false;      // MTG_SPILL=1: spill whenever the build runs in key ranges (tests)
     uint32_t hist_rows = 2048;     // MTG_HIST_ROWS: workgroups of the fused K1 histogram pass (tests
                                    // lower it so the grid-stride + prefetch loop runs on small inputs)
+    uint64_t d2h_piece = 16ull << 20;  // MTG_D2H_PIECE=bytes: the piece of the packed W / narrowed weights copy to
+                                   // the host (chunk_host.hpp), a multiple of 64 in [64, 1 Gi]
+    bool d2h_piece_set = false;    // MTG_D2H_PIECE given: arrays of any size go in pieces, not only those of
+                                   // 128 Mi rows / 16 Mi weights (tests run the piece loop on small inputs)
     bool fused_emit = true;        // MTG_FUSED_EMIT=0: K7 writes the lifted stream, K8 reads it (the
                                    // redundant-sink path)
     bool routed_min = false;       // MTG_ROUTED_CANON=min: the routed collect keeps min(fwd, rc)
@@ -462,6 +466,10 @@ static Knobs load_knobs() {
     if (const char *e = getenv("MTG_FUSED_MIN")) k.fused_min = strtoull(e, nullptr, 10);
     if (const char *e = getenv("MTG_RANGES")) k.force_ranges = (uint32_t)std::max(0L, std::min(4096L, atol(e)));
     if (const char *e = getenv("MTG_HIST_ROWS")) k.hist_rows = (uint32_t)std::max(1L, std::min(2048L, atol(e)));
+    if (const char *e = getenv("MTG_D2H_PIECE")) {
+        k.d2h_piece = std::max<uint64_t>(64, std::min<uint64_t>(strtoull(e, nullptr, 10), 1ull << 30) & ~63ull);
+        k.d2h_piece_set = true;
+    }
     return k;
 }
 
@@ -513,6 +521,7 @@ struct BuildState {
     double radix_ms = 0, radix_bytes = 0;
     uint64_t radix_launches = 0;
     double fused_ms = 0;  // device time of the last fused extract+partition launch
+    bool host_output = false;  // the build's arrays go to the host (build_chunk): it may spill (want_spill)
 };
 
 struct Ctx {
@@ -529,24 +538,12 @@ struct Ctx {
     mtg_boss_timings timings{};
     uint32_t epoch = 0;           // look-back granule epoch of the last launch
     size_t desc_words = 0;        // zeroed capacity of the descriptor buffer
-    int canon_mode = 1;            // the single-build extraction's canonical representative (cmode); the
-                                   // super-k-mer owners of a multi-GPU build extract with 2
     BuildState build;
-    // what the ABI layer reads after the build
-    bool host_output = false;      // the build's arrays go to the host (build_chunk): it may spill
-    std::vector<uint8_t> spill_W, spill_last;  // the spilled build's output rows (host)
-    std::vector<uint32_t> spill_weights;
-    uint64_t spilled_bytes = 0;    // bytes the last build kept outside HBM
 };
 
 static void reset_build_state(Ctx &c) { c.build = BuildState{}; }
 
 static inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
-
-// the extraction kernels' canonical argument: 0 basic, 1 min(fwd, rc), 2 the strand whose top 12 bits hash
-// smaller (boss_kernels.hpp: take_rc) -- any one representative per {x, rc x} gives the same real edges and
-// weights; 2 spreads the representatives over the key space (the multi-GPU collects, Ctx::canon_mode)
-static inline int cmode(const Ctx &c, bool canonical) { return canonical ? c.canon_mode : 0; }
 
 // zero the per-stage words; the error word is sticky for the whole build (checked at the end)
 static void reset_small(Ctx &c) {
@@ -558,6 +555,10 @@ static uint64_t read_u64(Ctx &c, const unsigned long long *p) {
     HIP_CHECK(hipMemcpyAsync(&v, p, sizeof(v), hipMemcpyDeviceToHost, c.stream));
     HIP_CHECK(hipStreamSynchronize(c.stream));
     return v;
+}
+
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // MTG_TRACE: host wall time since the previous trace point (stream drained first)

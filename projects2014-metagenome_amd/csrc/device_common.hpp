@@ -297,4 +297,16 @@ __global__ void read_index_kernel(const uint64_t *__restrict__ read_starts, uint
     }
 }
 
+// The bench's achievable-bandwidth copy: one 16-byte nontemporal vector load and store per thread
+// (global_load_dwordx4 / global_store_dwordx4 nt), a workgroup per 4 KiB.  tools/copy_bench.hip on
+// MI355X, 4 GiB (profiles/r6_copy_bench.txt): 6.44 TB/s -- above the guide's 6.29 float4 copy -- against
+// 6.21 for plain 16-byte accesses, 5.85 for round 5's 4 x (2 x 8-byte nt) per thread (the kernel this
+// replaces: its 8-byte nt halves), 4.6-4.95 for grid-stride loops, 4.96 for hipMemcpyAsync D2D.
+typedef unsigned int mtg_u32x4 __attribute__((ext_vector_type(4)));
+extern "C" __global__ __launch_bounds__(256) void copy16_kernel(const mtg_u32x4 *__restrict__ src,
+                                                                mtg_u32x4 *__restrict__ dst, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);
+}
+
 }  // namespace mtg

@@ -263,6 +263,17 @@ __global__ void kmc_decode_kernel(const uint8_t *__restrict__ rec, const uint64_
     }
 }
 
+// the records of database m (on the device at drec, its prefix table at dlut) -> reads at seq + seq_base and,
+// with starts, their starts and counts from read index read_base; the caller checks the launch
+static void launch_kmc_decode(const KmcInput &m, const uint8_t *drec, const uint64_t *dlut, uint8_t *seq,
+                              uint64_t seq_base, uint64_t *starts, uint32_t *counts, uint64_t read_base,
+                              hipStream_t s) {
+    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((m.total + 255) / 256, 65536));
+    kmc_decode_kernel<<<dim3((unsigned)grid), dim3(256), 0, s>>>(drec, dlut, m.nlut, m.total, m.k, m.lut_len,
+                                                                m.counter_size, m.min_count, m.max_count,
+                                                                m.both ? 1 : 0, seq, seq_base, starts, counts, read_base);
+}
+
 // ------------------------------------------------------------------------ KMC1 writer
 //
 // The builder's own k-mer counter output, for the KMC input of BASELINE config 5 (`metagraph
