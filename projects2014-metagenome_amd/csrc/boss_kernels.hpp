@@ -8,6 +8,7 @@
 
 #include "device_common.hpp"
 #include "keys.hpp"
+#include "tile_scatter.hpp"
 
 namespace mtg {
 
@@ -622,50 +623,26 @@ __global__ __launch_bounds__(512) void rc_partition_gapped_kernel(
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j)
         if (src[j] != ~0ull) k[j] = keys[src[j]];
+    const auto bucket_of = [=](const Key<L> &key) { return bits_at(key, 2 * K - hb, hb); };
     uint32_t r[ITEMS];
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
         r[j] = 0xFFFFFFFFu;
         if (src[j] == ~0ull) continue;
         k[j] = revcomp2(k[j], K);
-        r[j] = atomicAdd(&s_cnt[bits_at(k[j], 2 * K - hb, hb)], 1u);
+        r[j] = atomicAdd(&s_cnt[bucket_of(k[j])], 1u);
     }
     __syncthreads();
-    uint32_t c[PER];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        c[q] = i < nbk ? s_cnt[i] : 0;
-        sum += c[q];
-    }
-    uint32_t total;
-    uint32_t off = block_exclusive_sum<BLOCK>(sum, s_scan, &total);
-    // (the run reservations stay in flight across the LDS scatter, as in the partition passes)
-    unsigned long long gq[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        gq[q] = 0;
-        if (i < nbk) {
-            s_loff[i] = off;
-            if (c[q]) gq[q] = atomicAdd(&cursor[i], (unsigned long long)c[q]);
-        }
-        off += c[q];
-    }
+    // tile_scatter.hpp; one cursor per level-1 bucket and no ends (the histogram pass counted these keys)
+    const TileRuns<PER> runs = tile_reserve_runs<BLOCK, PER, false>(s_cnt, s_loff, s_scan, nbk, cursor, PlainBuckets{});
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j)
-        if (r[j] != 0xFFFFFFFFu) s_keys[s_loff[bits_at(k[j], 2 * K - hb, hb)] + r[j]] = k[j];
-#pragma unroll
-    for (int q = 0; q < PER; ++q)
-        if (tid * PER + q < nbk) s_gbase[tid * PER + q] = gq[q];
+        if (r[j] != 0xFFFFFFFFu) s_keys[s_loff[bucket_of(k[j])] + r[j]] = k[j];
+    tile_publish_runs(runs, nbk, PlainBuckets{}, s_gbase);
     __syncthreads();
-    for (uint32_t q = tid; q < total; q += BLOCK) {
-        const Key<L> key = s_keys[q];
-        const uint32_t b = bits_at(key, 2 * K - hb, hb);
-        out[s_gbase[b] + (q - s_loff[b])] = key;
-    }
+    tile_write_runs<BLOCK>(s_keys, s_loff, s_gbase, runs.total, PlainBuckets{}, bucket_of,
+                           [=](uint64_t o, const Key<L> &key, uint32_t) { out[o] = key; });
 }
 
 /*

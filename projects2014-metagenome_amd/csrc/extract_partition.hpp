@@ -14,6 +14,7 @@
 
 #include "boss_kernels.hpp"
 #include "msd_sort.hpp"
+#include "tile_scatter.hpp"
 
 namespace mtg {
 
@@ -249,6 +250,17 @@ __global__ __launch_bounds__(256) void extract_hist_wide_kernel(const uint8_t *_
     for (uint32_t i = tid; i < NB; i += BLOCK) rows[(uint64_t)blockIdx.x * NB + i] = s_h[i];
 }
 
+// Pass B's buckets for tile_scatter.hpp: one set of cursors and ends per stripe of tiles
+// (stripe_cursor_kernel), bucket i of this tile's stripe at (tile / per_stripe) * nb + i
+struct StripeBuckets {
+    uint64_t tile, per_stripe;
+    uint32_t nb;
+    const unsigned long long *bend;
+    __device__ __forceinline__ size_t cursor(uint32_t i) const { return (size_t)(tile / per_stripe) * nb + i; }
+    __device__ __forceinline__ constexpr bool checked() const { return true; }
+    __device__ __forceinline__ unsigned long long end(uint32_t, size_t ci) const { return bend[ci]; }
+};
+
 template <bool COUNTED, int BLOCK_ = COUNTED ? 512 : 1024>
 struct FusedTraits {
     static constexpr int BLOCK = BLOCK_;  // the LDS tile: BLOCK * PPT keys (16 K at 1024 threads)
@@ -307,68 +319,30 @@ __global__ __launch_bounds__(BLOCK_) void extract_partition_kernel(
             if (!((s_sel[pb >> 5] >> (pb & 31)) & 1u)) m &= ~(1u << j);
         }
     }
+    const auto bucket_of = [=](const Key<L> &key) { return key_prefix(key, 2 * K, b); };
     uint32_t r[PPT];
 #pragma unroll
-    for (int j = 0; j < PPT; ++j)
-        r[j] = (m & (1u << j)) ? atomicAdd(&s_cnt[key_prefix(kk[j], 2 * K, b)], 1u) : 0u;
+    for (int j = 0; j < PPT; ++j) r[j] = (m & (1u << j)) ? atomicAdd(&s_cnt[bucket_of(kk[j])], 1u) : 0u;
     __syncthreads();
-    uint32_t c[PER];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        c[q] = i < nb ? s_cnt[i] : 0;
-        sum += c[q];
-    }
-    uint32_t total;
-    uint32_t off = block_exclusive_sum<BLOCK>(sum, s_scan, &total);
-    __syncthreads();  // every count is read before the offsets overwrite them
-    // (the run reservations stay in flight across the LDS scatter, as in extract_partition_fast_kernel)
-    unsigned long long gq[PER], be[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        gq[q] = 0, be[q] = 0;
-        if (i < nb) {
-            s_cnt[i] = off;
-            const size_t ci = (size_t)(tile / per_stripe) * nb + i;  // this tile's stripe
-            if (c[q]) {
-                gq[q] = atomicAdd(&cursor[ci], (unsigned long long)c[q]);
-                be[q] = bend[ci];
-            }
-        }
-        off += c[q];
-    }
+    // tile_scatter.hpp; here the offsets overwrite the counts in s_cnt
+    const StripeBuckets at{tile, per_stripe, nb, bend};
+    const TileRuns<PER> runs = tile_reserve_runs<BLOCK, PER, true>(s_cnt, s_cnt, s_scan, nb, cursor, at);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
         if (m & (1u << j)) {
-            const uint32_t pos = s_cnt[key_prefix(kk[j], 2 * K, b)] + r[j];
+            const uint32_t pos = s_cnt[bucket_of(kk[j])] + r[j];
             s_keys[pos] = kk[j];
             if (COUNTED) s_vals[pos] = cc[j];
         }
     }
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        if (i < nb) {
-            unsigned long long g = gq[q];
-            if (c[q] && g + c[q] > be[q]) {  // pass A counted this bucket differently: never
-                atomicOr(error, 2u);          // write past its range (the host raises)
-                g = ~0ull;
-            }
-            s_gbase[i] = g;
-        }
-    }
+    tile_publish_runs(runs, nb, at, s_gbase, [=] { atomicOr(error, 2u); });
     __syncthreads();
-    for (uint32_t p = tid; p < total; p += BLOCK) {
-        const Key<L> key = s_keys[p];
-        const uint32_t lb = key_prefix(key, 2 * K, b);
-        if (s_gbase[lb] == ~0ull) continue;
-        const uint64_t o = s_gbase[lb] + (p - s_cnt[lb]);
-        kout[o] = key;
-        if (COUNTED) vout[o] = s_vals[p];
-    }
+    tile_write_runs<BLOCK>(s_keys, s_cnt, s_gbase, runs.total, at, bucket_of,
+                           [=](uint64_t o, const Key<L> &key, uint32_t p) {
+                               kout[o] = key;
+                               if (COUNTED) vout[o] = s_vals[p];
+                           });
 }
 
 // Pass B without counts for K <= 32 (u64 keys), VALU-lean: the tile's read bytes are packed once
@@ -386,10 +360,8 @@ __global__ __launch_bounds__(BLOCK) void extract_partition_fast_kernel(
     uint64_t per_stripe, unsigned long long *__restrict__ cursor, const unsigned long long *__restrict__ bend,
     Key<1> *__restrict__ kout, uint32_t *__restrict__ error, const uint32_t *__restrict__ sel = nullptr,
     uint32_t *__restrict__ povf = nullptr, const long long *__restrict__ bdelta = nullptr) {
-    // povf (the speculative level-1 layout): a reservation past its segment's end writes nothing and
-    // raises *povf instead of the error word -- the caller then runs the exact passes A and B
-    // bdelta (the collect rounds' one pass B): bucket i's keys go bdelta[i] elements away from their
-    // layout position (each round's buckets into that round's buffer)
+    // povf (the speculative level-1 layout): raised instead of the error word by a run past its segment's
+    // end -- the caller then runs the exact passes A and B; bend, bdelta: tile_scatter.hpp
     const unsigned K = KC ? (unsigned)KC : K_;
     const int canonical = CM >= 0 ? CM : canonical_;
     constexpr int PPT = 16, TILE = BLOCK * PPT, NW = BLOCK + 2;  // +2 words: the last thread's overhang
@@ -477,71 +449,29 @@ __global__ __launch_bounds__(BLOCK) void extract_partition_fast_kernel(
         m |= (uint32_t)((uint32_t)j < nwin && ((inv >> j) & maskK) == 0) << j;
     }
     const unsigned bshift = 2 * K - b;
+    const auto bucket_of = [=](uint64_t key) { return (uint32_t)(key >> bshift); };
     if (sel) {  // one round of a batched collect: only the level-1 buckets of its mask
 #pragma unroll
         for (int j = 0; j < PPT; ++j) {
-            const uint32_t pb = (uint32_t)(kk[j] >> bshift);
+            const uint32_t pb = bucket_of(kk[j]);
             if (!((s_sel[pb >> 5] >> (pb & 31)) & 1u)) m &= ~(1u << j);
         }
     }
     uint32_t r[PPT];
 #pragma unroll
-    for (int j = 0; j < PPT; ++j)
-        r[j] = (m & (1u << j)) ? atomicAdd(&s_cnt[(uint32_t)(kk[j] >> bshift)], 1u) : 0u;
+    for (int j = 0; j < PPT; ++j) r[j] = (m & (1u << j)) ? atomicAdd(&s_cnt[bucket_of(kk[j])], 1u) : 0u;
     __syncthreads();
-    uint32_t c[PER];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        c[q] = i < nb ? s_cnt[i] : 0;
-        sum += c[q];
-    }
-    uint32_t total;
-    uint32_t off = block_exclusive_sum<BLOCK>(sum, s_scan, &total);
-    __syncthreads();  // every count is read before the run bases overwrite them
-    // (round 5) the run reservations are issued here and consumed after the LDS scatter below, so their
-    // round trip to the cursors overlaps the scatter instead of stalling the workgroup before it
-    unsigned long long gq[PER], be[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        gq[q] = 0, be[q] = 0;
-        if (i < nb) {
-            s_off[i] = (uint16_t)off;
-            const size_t ci = (size_t)(tile / per_stripe) * nb + i;  // this tile's stripe
-            if (c[q]) {
-                gq[q] = atomicAdd(&cursor[ci], (unsigned long long)c[q]);
-                be[q] = bend[ci];
-            }
-        }
-        off += c[q];
-    }
+    // tile_scatter.hpp; u16 offsets, the counts in the run-base array
+    const StripeBuckets at{tile, per_stripe, nb, bend};
+    const TileRuns<PER> runs = tile_reserve_runs<BLOCK, PER, true>(s_cnt, s_off, s_scan, nb, cursor, at);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < PPT; ++j)
-        if (m & (1u << j)) s_keys[s_off[(uint32_t)(kk[j] >> bshift)] + r[j]] = kk[j];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        if (i < nb) {
-            unsigned long long g = gq[q];
-            if (c[q] && g + c[q] > be[q]) {  // pass A counted this bucket differently: never
-                atomicOr(povf ? povf : error, povf ? 1u : 2u);  // write past its range
-                g = ~0ull;
-            } else if (bdelta) {
-                g += (unsigned long long)bdelta[i];
-            }
-            s_gbase[i] = g;
-        }
-    }
+        if (m & (1u << j)) s_keys[s_off[bucket_of(kk[j])] + r[j]] = kk[j];
+    tile_publish_runs(runs, nb, at, s_gbase, [=] { atomicOr(povf ? povf : error, povf ? 1u : 2u); }, bdelta);
     __syncthreads();
-    for (uint32_t p = tid; p < total; p += BLOCK) {
-        const uint64_t key = s_keys[p];
-        const uint32_t lb = (uint32_t)(key >> bshift);
-        if (s_gbase[lb] == ~0ull) continue;
-        kout[s_gbase[lb] + (p - s_off[lb])].w[0] = key;
-    }
+    tile_write_runs<BLOCK>(s_keys, s_off, s_gbase, runs.total, at, bucket_of,
+                           [=](uint64_t o, uint64_t key, uint32_t) { kout[o].w[0] = key; });
 }
 
 // Pass B for u128 windows (33 <= K <= 64, BASELINE configs[2]'s k = 63), VALU-lean like the u64 kernel
@@ -561,7 +491,7 @@ __global__ __launch_bounds__(BLOCK) void extract_partition_fast2_kernel(
     uint64_t per_stripe, unsigned long long *__restrict__ cursor, const unsigned long long *__restrict__ bend,
     Key<2> *__restrict__ kout, uint32_t *__restrict__ error, const uint32_t *__restrict__ sel = nullptr,
     const long long *__restrict__ bdelta = nullptr) {
-    // bdelta: as in extract_partition_fast_kernel (the collect rounds' one pass B for configs[2]'s two rounds)
+    // bdelta: tile_scatter.hpp (here for configs[2]'s two rounds)
     const unsigned K = KC ? (unsigned)KC : K_;
     static_assert(PPT_ == 16 || PPT_ == 8, "16 or 8 windows a thread");
     constexpr int PPT = PPT_, TILE = BLOCK * PPT, NW = TILE / 16 + 5;  // +5 words: a thread's windows reach 15 + 63 chars on
@@ -675,58 +605,18 @@ __global__ __launch_bounds__(BLOCK) void extract_partition_fast2_kernel(
 #pragma unroll
     for (int j = 0; j < PPT; ++j) r[j] = (m & (1u << j)) ? atomicAdd(&s_cnt[digit(kk[j])], 1u) : 0u;
     __syncthreads();
-    uint32_t c[PER];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        c[q] = i < nb ? s_cnt[i] : 0;
-        sum += c[q];
-    }
-    uint32_t total;
-    uint32_t off = block_exclusive_sum<BLOCK>(sum, s_scan, &total);
-    __syncthreads();  // every count is read before the run bases overwrite them
-    // (the run reservations stay in flight across the LDS scatter, as in extract_partition_fast_kernel)
-    unsigned long long gq[PER], be[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        gq[q] = 0, be[q] = 0;
-        if (i < nb) {
-            s_off[i] = (uint16_t)off;
-            const size_t ci = (size_t)(tile / per_stripe) * nb + i;  // this tile's stripe
-            if (c[q]) {
-                gq[q] = atomicAdd(&cursor[ci], (unsigned long long)c[q]);
-                be[q] = bend[ci];
-            }
-        }
-        off += c[q];
-    }
+    // tile_scatter.hpp; u16 offsets, the counts in the run-base array
+    const StripeBuckets at{tile, per_stripe, nb, bend};
+    const TileRuns<PER> runs = tile_reserve_runs<BLOCK, PER, true>(s_cnt, s_off, s_scan, nb, cursor, at);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < PPT; ++j)
         if (m & (1u << j)) s_keys[s_off[digit(kk[j])] + r[j]] = kk[j];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        if (i < nb) {
-            unsigned long long g = gq[q];
-            if (c[q] && g + c[q] > be[q]) {  // pass A counted this bucket differently: never
-                atomicOr(error, 2u);          // write past its range
-                g = ~0ull;
-            } else if (bdelta) {
-                g += (unsigned long long)bdelta[i];
-            }
-            s_gbase[i] = g;
-        }
-    }
+    tile_publish_runs(runs, nb, at, s_gbase, [=] { atomicOr(error, 2u); }, bdelta);
     __syncthreads();
-    for (uint32_t p = tid; p < total; p += BLOCK) {
-        const ulonglong2 key = s_keys[p];
-        const uint32_t lb = digit(key);
-        if (s_gbase[lb] == ~0ull) continue;
-        *reinterpret_cast<ulonglong2 *>(&kout[s_gbase[lb] + (p - s_off[lb])]) = key;
-    }
+    tile_write_runs<BLOCK>(s_keys, s_off, s_gbase, runs.total, at, digit, [=](uint64_t o, const ulonglong2 &key, uint32_t) {
+        *reinterpret_cast<ulonglong2 *>(&kout[o]) = key;
+    });
 }
 
 // Pass B's write cursors, one set per stripe.  All tiles scatter into the same 2^b level-1

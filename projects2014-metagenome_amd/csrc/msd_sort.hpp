@@ -18,6 +18,7 @@
 
 #include "device_common.hpp"
 #include "keys.hpp"
+#include "tile_scatter.hpp"
 
 namespace mtg {
 
@@ -233,6 +234,17 @@ __device__ __forceinline__ void store_key(Key<L> *p, const Key<L> &k, bool nt) {
     }
 }
 
+// msd_partition_kernel's window buckets for tile_scatter.hpp: window bucket i is bucket wbase + i, the
+// cursors cstride apart, the ends one per bucket and there when bend is not null
+struct WindowBuckets {
+    const unsigned long long *bend;
+    uint32_t wbase;
+    unsigned cstride;
+    __device__ __forceinline__ size_t cursor(uint32_t i) const { return (size_t)(wbase + i) * cstride; }
+    __device__ __forceinline__ bool checked() const { return bend != nullptr; }
+    __device__ __forceinline__ unsigned long long end(uint32_t i, size_t) const { return bend[wbase + i]; }
+};
+
 template <int L, bool HAS_VAL, int BLOCK = MSD_BLOCK, bool NT = false>
 __global__ __launch_bounds__(BLOCK) void msd_partition_kernel(
     const Key<L> *__restrict__ kin, Key<L> *__restrict__ kout, const uint32_t *__restrict__ vin,
@@ -243,8 +255,8 @@ __global__ __launch_bounds__(BLOCK) void msd_partition_kernel(
     // tvalid (the speculative level-1 layout): tile t holds keys only in its first tvalid[t] positions
     // NT: nontemporal loads and stores (the streaming wide-digit pass: nothing it touches is
     // re-read from L2; measured 4.65 vs 4.67 ms on the cfg2 pass)
-    // bend (speculative buckets, sized from a sample): a reservation past its bucket's end writes
-    // nothing and raises *povf -- the caller then partitions again from the exact histogram
+    // bend, povf (speculative buckets, sized from a sample; tile_scatter.hpp): after *povf the caller
+    // partitions again from the exact histogram
     constexpr int ITEMS = MsdTraits<L>::ITEMS;
     constexpr int TILE = ITEMS * BLOCK;
     constexpr int WMAX = MSD_WIN << 8;
@@ -299,65 +311,28 @@ __global__ __launch_bounds__(BLOCK) void msd_partition_kernel(
         }
     }
     __syncthreads();
-    // exclusive scan of the window counts (wsize <= 1024: two per thread)
+    // tile_scatter.hpp over the window's buckets (wsize <= 1024: two per thread); the ends are optional
+    // and one per bucket, the cursors cstride apart
     constexpr int PER = WMAX / BLOCK > 0 ? WMAX / BLOCK : 1;
-    uint32_t c[PER];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        c[q] = i < wsize ? s_cnt[i] : 0;
-        sum += c[q];
-    }
-    uint32_t total;
-    uint32_t off = block_exclusive_sum<BLOCK>(sum, s_scan, &total);
-    // (round 5) the run reservations are issued here and consumed after the LDS scatter below, so their
-    // round trip to the cursors overlaps the scatter
-    unsigned long long gq[PER], be[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        gq[q] = 0, be[q] = 0;
-        if (i < wsize) {
-            s_loff[i] = off;
-            if (c[q]) {
-                gq[q] = atomicAdd(&cursor[(size_t)(wbase + i) * cstride], (unsigned long long)c[q]);
-                if (bend) be[q] = bend[wbase + i];
-            }
-        }
-        off += c[q];
-    }
+    const auto bucket_of = [=](const Key<L> &key) { return key_prefix(key, nbits, b) - wbase; };
+    const WindowBuckets at{bend, wbase, cstride};
+    const TileRuns<PER> runs = tile_reserve_runs<BLOCK, PER, false>(s_cnt, s_loff, s_scan, wsize, cursor, at);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
         if (r[j] != 0xFFFFFFFFu) {
-            const uint32_t lb = key_prefix(k[j], nbits, b) - wbase;
-            const uint32_t pos = s_loff[lb] + r[j];
+            const uint32_t pos = s_loff[bucket_of(k[j])] + r[j];
             s_keys[pos] = k[j];
             if (HAS_VAL) s_vals[pos] = v[j];
         }
     }
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t i = tid * PER + q;
-        if (i < wsize) {
-            unsigned long long gb = gq[q];
-            if (bend && c[q] && gb + c[q] > be[q]) {
-                *povf = 1u;
-                gb = ~0ull;  // this run is not written
-            }
-            s_gbase[i] = gb;
-        }
-    }
+    tile_publish_runs(runs, wsize, at, s_gbase, [=] { *povf = 1u; });
     __syncthreads();
-    for (uint32_t p = tid; p < total; p += BLOCK) {
-        const Key<L> key = s_keys[p];
-        const uint32_t lb = key_prefix(key, nbits, b) - wbase;
-        if (bend && s_gbase[lb] == ~0ull) continue;
-        const uint64_t o = s_gbase[lb] + (p - s_loff[lb]);
-        store_key(kout + o, key, NT);
-        if (HAS_VAL) vout[o] = s_vals[p];
-    }
+    tile_write_runs<BLOCK>(s_keys, s_loff, s_gbase, runs.total, at, bucket_of,
+                           [=](uint64_t o, const Key<L> &key, uint32_t p) {
+                               store_key(kout + o, key, NT);
+                               if (HAS_VAL) vout[o] = s_vals[p];
+                           });
 }
 
 // Group boundaries over buckets (buckets never split): bucket b opens a group when it crosses
