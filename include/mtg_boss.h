@@ -30,7 +30,8 @@
  * The suffix-sharded route itself (`build --suffix-len`, `concatenate --clear-dummy`,
  * cli/build.cpp:102-155, 358-456) runs too: a constructor created with a filter_suffix builds the
  * chunk of that node suffix, and mtg_boss_write_dbg with mask_dummy = 2 prunes the concatenated
- * chunks' redundant source dummies.
+ * chunks' redundant source dummies (on the device: mtg_boss_chunk_extend_device, then
+ * mtg_boss_write_dbg_device_pruned).
  *
  * No torch types, no C++ types: plain pointers and sizes.  All functions are thread-safe
  * except that one constructor must not be built and added to at the same time.
@@ -326,9 +327,10 @@ int mtg_boss_write_dbg(const mtg_boss_chunk *chunk, const char *outbase, int gra
  * stages (W's wavelet-tree bits, the rank words, the suffix-range index, the valid-edge mask, the
  * weights' int_vector) run as kernels (csrc/dbg_device.hpp); the Huffman shape, the select supports,
  * bit_vector_small and the framing stay host code.  <outbase>.dbg.weights is written when weights !=
- * NULL and bits_per_count != 0.  mask_dummy: 0 or 1; 2 (pruning) returns MTG_ERR_UNSUPPORTED: copy the
- * chunk to the host and use mtg_boss_write_dbg.  A row with W >= 16 returns MTG_ERR_ARGUMENT before any
- * file is written.  graph_mode, suffix_length and *n_valid as for mtg_boss_write_dbg.
+ * NULL and bits_per_count != 0.  mask_dummy: 0 or 1; 2 (pruning) returns MTG_ERR_UNSUPPORTED here: call
+ * mtg_boss_write_dbg_device_pruned below (or copy the chunk to the host and use mtg_boss_write_dbg).  A
+ * row with W >= 16 returns MTG_ERR_ARGUMENT before any file is written.  graph_mode, suffix_length and
+ * *n_valid as for mtg_boss_write_dbg.
  */
 typedef struct mtg_dbg_write_timings {
     double device_ms;    /* kernels, events on the constructor's stream */
@@ -340,6 +342,42 @@ int mtg_boss_write_dbg_device(mtg_boss_ctor *ctor, const mtg_boss_device_chunk *
                               uint8_t bits_per_count, const char *outbase, int graph_mode,
                               int mask_dummy, int64_t suffix_length, uint64_t *n_valid,
                               mtg_dbg_write_timings *timings /* may be NULL */);
+
+/*
+ * `concatenate --clear-dummy` from a chunk in device memory: the device counterpart of mtg_boss_write_dbg
+ * with mask_dummy = 2, bit for bit.  The redundant source dummies of the concatenated suffix chunks are
+ * found and erased on the device (csrc/dbg_prune.hpp: the single-incoming flags, the source-dummy tree
+ * walked down level by level and reduced back up, BOSS::erase_edges as a compaction), then <outbase>.dbg
+ * and <outbase>.edgemask are written from the pruned arrays, and no weights file.  The chunk's arrays are
+ * only read; mutex, stream and scratch as for mtg_boss_write_dbg_device.  *n_valid, *n_erased (the rows
+ * the pruning removed) and timings may be NULL.  Arrays that are no BOSS table (a source-dummy tree that
+ * outgrows the rows) return MTG_ERR_ARGUMENT before any file is written.
+ */
+int mtg_boss_write_dbg_device_pruned(mtg_boss_ctor *ctor, const mtg_boss_device_chunk *chunk,
+                                     const char *outbase, int graph_mode, int64_t suffix_length,
+                                     uint64_t *n_valid, uint64_t *n_erased,
+                                     mtg_dbg_write_timings *timings /* may be NULL */);
+
+/*
+ * BOSS::erase_edges (boss.cpp:1342-1403) alone, on the device: the rows of `in` with d_erase[i] == 0 go
+ * to `out` in order.  An erased row's `last` moves to the previous kept row (not to row 0), a minus label
+ * c + 5 whose class lost a plain c since its previous kept row becomes c, F counts the kept rows.
+ * d_erase: one byte per row on the device, row 0 must be 0.  out->W and out->last are caller-allocated
+ * device arrays of in->n bytes, distinct from the input's; out->k, out->n and out->F are filled, weights
+ * are not carried.  `in` is only read.
+ */
+int mtg_boss_erase_edges_device(mtg_boss_ctor *ctor, const mtg_boss_device_chunk *in, const uint8_t *d_erase,
+                                mtg_boss_device_chunk *out);
+
+/*
+ * BOSS::Chunk::extend (boss_chunk.cpp:230-270) on caller-owned device arrays of dst_capacity_rows rows:
+ * rows 1.. of src are appended to dst with device-to-device copies, F, n_real and n_dummy are summed; a
+ * src of one row is a no-op.  A dst of no rows (n == 0) takes src whole.  A constructor's own device
+ * chunk lives until its next build: extend each suffix chunk into such a buffer, then prune the buffer.
+ * MTG_ERR_ARGUMENT when k differs, when the capacity is too small, or when exactly one side has weights.
+ */
+int mtg_boss_chunk_extend_device(mtg_boss_ctor *ctor, mtg_boss_device_chunk *dst, uint64_t dst_capacity_rows,
+                                 const mtg_boss_device_chunk *src);
 
 /* One sdsl-lite container of the graph files written alone to `path` (the layout tests): kind 0
  * bit_vector_stat over `nbits` bits of `data`, 1 bit_vector_small (sd_vector or rrr_vector<63>,

@@ -118,7 +118,8 @@ EXPORTS = ("mtg_boss_abi_version", "mtg_last_error", "mtg_boss_ctor_create",
            "mtg_boss_ctor_add_fasta", "mtg_device_copy", "mtg_kmc_load_device",
            "mtg_device_reads_free", "mtg_kmc_write_device", "mtg_host_pool_bytes",
            "mtg_host_pool_trim", "mtg_comm_create_callbacks", "mtg_comm_local_held_ms",
-           "mtg_boss_ctor_trim", "mtg_boss_write_dbg_device")
+           "mtg_boss_ctor_trim", "mtg_boss_write_dbg_device", "mtg_boss_write_dbg_device_pruned",
+           "mtg_boss_erase_edges_device", "mtg_boss_chunk_extend_device")
 
 COMM_ID_BYTES = 128
 
@@ -206,6 +207,13 @@ def lib():
         L.mtg_boss_write_dbg_device.argtypes = [ctypes.c_void_p, P(_DeviceChunk), ctypes.c_uint8,
                                                 ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                                 P(ctypes.c_uint64), P(DbgWriteTimings)]
+        L.mtg_boss_write_dbg_device_pruned.argtypes = [ctypes.c_void_p, P(_DeviceChunk), ctypes.c_char_p,
+                                                       ctypes.c_int, ctypes.c_int64, P(ctypes.c_uint64),
+                                                       P(ctypes.c_uint64), P(DbgWriteTimings)]
+        L.mtg_boss_erase_edges_device.argtypes = [ctypes.c_void_p, P(_DeviceChunk), ctypes.c_void_p,
+                                                  P(_DeviceChunk)]
+        L.mtg_boss_chunk_extend_device.argtypes = [ctypes.c_void_p, P(_DeviceChunk), ctypes.c_uint64,
+                                                   P(_DeviceChunk)]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -321,6 +329,49 @@ class Chunk:
             self.weights = np.concatenate([self.weights, other.weights[1:]])
 
 
+class DeviceChunkBuffer:
+    """Device arrays of `capacity` rows (mtg_device_alloc) that suffix chunks are concatenated into,
+    as Chunk.extend concatenates them on the host: a constructor's own device chunk lives only until
+    its next build.  `chunk` is the _DeviceChunk over the rows so far, ready for write_dbg_device."""
+
+    def __init__(self, ctor, k, capacity, weighted=False, device_id=0):
+        self._ctor = ctor  # any constructor on the device: its mutex and stream carry the copies
+        self.capacity = int(capacity)
+        self._ptrs = []
+        self.chunk = _DeviceChunk(k=k, n=0)
+        self.chunk.W = self._alloc(device_id, self.capacity)
+        self.chunk.last = self._alloc(device_id, self.capacity)
+        if weighted:
+            self.chunk.weights = self._alloc(device_id, 4 * self.capacity)
+
+    def _alloc(self, device_id, nbytes):
+        p = lib().mtg_device_alloc(device_id, max(nbytes, 1))
+        if not p:
+            raise RuntimeError(lib().mtg_last_error().decode() or "mtg_device_alloc failed")
+        self._ptrs.append(p)
+        return p
+
+    def extend(self, device_chunk):
+        """BOSS::Chunk::extend with a device chunk (mtg_boss_chunk_extend_device)."""
+        _check(lib().mtg_boss_chunk_extend_device(self._ctor._h, ctypes.byref(self.chunk), self.capacity,
+                                                  ctypes.byref(device_chunk)))
+
+    def free(self):
+        ptrs, self._ptrs = getattr(self, "_ptrs", []), []
+        for p in ptrs:
+            if _lib is not None:
+                _lib.mtg_device_free(p)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        self.free()
+
+
 def generate_suffixes(length):
     """KmerExtractorBOSS::generate_suffixes (kmer/kmer_extractor.cpp:402-416): the node suffixes
     of `build --suffix-len` in BOSS order (last char slowest, common/utils/string_utils.cpp:82-95),
@@ -345,6 +396,7 @@ class BOSSChunkConstructor:
         self._bits = bits_per_count
         self._canonical = canonical
         self.last_dbg_timings = None  # the split of the last write_dbg_device call
+        self.last_dbg_erased = None   # the rows its pruning removed (prune=True)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -454,18 +506,37 @@ class BOSSChunkConstructor:
                                                     ctypes.byref(c)))
         return c
 
-    def write_dbg_device(self, chunk, outbase, canonical=False, mask_dummy=False, suffix_length=-1):
+    def write_dbg_device(self, chunk, outbase, canonical=False, mask_dummy=False, suffix_length=-1,
+                         prune=False):
         """Chunk.write_dbg from a chunk in device memory (mtg_boss_write_dbg_device): `chunk` is the
         descriptor build_device returned or a _DeviceChunk over uploaded arrays.  The same bytes as
         the host writer; the per-row stages run on the GPU.  Returns the valid edges after masking,
-        else rows - 1; last_dbg_timings holds the call's device / copy / host split."""
+        else rows - 1; last_dbg_timings holds the call's device / copy / host split.
+        prune=True is Chunk.write_dbg(prune=True) on the device (mtg_boss_write_dbg_device_pruned):
+        the redundant source dummies are erased, the mask is written and no weights file;
+        last_dbg_erased then holds the rows the pruning removed."""
         nv = ctypes.c_uint64(0)
         t = DbgWriteTimings()
+        if prune:
+            ne = ctypes.c_uint64(0)
+            _check(lib().mtg_boss_write_dbg_device_pruned(self._h, ctypes.byref(chunk), os.fsencode(outbase),
+                                                          int(bool(canonical)), int(suffix_length),
+                                                          ctypes.byref(nv), ctypes.byref(ne), ctypes.byref(t)))
+            self.last_dbg_timings = t.as_dict()
+            self.last_dbg_erased = ne.value
+            return nv.value
         _check(lib().mtg_boss_write_dbg_device(self._h, ctypes.byref(chunk), self._bits or 0,
                                                os.fsencode(outbase), int(bool(canonical)), int(mask_dummy),
                                                int(suffix_length), ctypes.byref(nv), ctypes.byref(t)))
         self.last_dbg_timings = t.as_dict()
         return nv.value
+
+    def erase_edges_device(self, chunk, d_erase, out):
+        """BOSS::erase_edges on the device (mtg_boss_erase_edges_device): the rows of `chunk` whose byte of
+        d_erase (a device pointer, one byte per row, row 0 must be 0) is 0 go to `out`, a _DeviceChunk
+        whose W and last are device arrays of chunk.n bytes; out.k, out.n and out.F are filled."""
+        _check(lib().mtg_boss_erase_edges_device(self._h, ctypes.byref(chunk), d_erase, ctypes.byref(out)))
+        return out
 
     def timings(self):
         t = Timings()

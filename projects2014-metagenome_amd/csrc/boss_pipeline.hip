@@ -3236,6 +3236,22 @@ static int bad_arguments(const char *msg = "bad arguments") {
     return MTG_ERR_ARGUMENT;
 }
 
+// the device graph entries after mtg_boss_write_dbg_device share this: the constructor's mutex and device, DbgArgumentError -> MTG_ERR_ARGUMENT
+template <class F>
+static int dbg_device_call(mtg_boss_ctor *c, F &&f) {
+    std::lock_guard<std::mutex> lock(c->mu);
+    return abi_call(MTG_ERR_DEVICE, [&] {
+        try {
+            HIP_CHECK(hipSetDevice(c->device));
+            f();
+            return MTG_OK;
+        } catch (const DbgArgumentError &e) {  // the caller's arrays are no BOSS table
+            set_error(e.what());
+            return MTG_ERR_ARGUMENT;
+        }
+    });
+}
+
 extern "C" {
 
 int mtg_boss_abi_version(void) { return MTG_BOSS_ABI_VERSION; }
@@ -3944,6 +3960,40 @@ int mtg_boss_write_dbg_device(mtg_boss_ctor *c, const mtg_boss_device_chunk *chu
             return MTG_ERR_ARGUMENT;
         }
     });
+}
+
+int mtg_boss_write_dbg_device_pruned(mtg_boss_ctor *c, const mtg_boss_device_chunk *chunk, const char *outbase,
+                                     int graph_mode, int64_t suffix_length, uint64_t *n_valid, uint64_t *n_erased,
+                                     mtg_dbg_write_timings *timings) {
+    if (!c || !chunk || !outbase || !chunk->W || !chunk->last || chunk->n < 1 || graph_mode < 0 || graph_mode > 1)
+        return bad_arguments("write_dbg_device_pruned: bad arguments");
+    return dbg_device_call(c, [&] {
+        uint64_t erased = 0;
+        const uint64_t v = write_dbg_device_pruned_impl(c->ctx, *chunk, outbase, (uint64_t)graph_mode, suffix_length,
+                                                        &erased, timings);
+        if (n_valid) *n_valid = v;
+        if (n_erased) *n_erased = erased;
+    });
+}
+
+int mtg_boss_erase_edges_device(mtg_boss_ctor *c, const mtg_boss_device_chunk *in, const uint8_t *d_erase,
+                                mtg_boss_device_chunk *out) {
+    if (!c || !in || !d_erase || !out || !in->W || !in->last || in->n < 1 || !out->W || !out->last ||
+        out->W == in->W || out->last == in->last)
+        return bad_arguments("erase_edges_device: bad arguments");
+    return dbg_device_call(c, [&] { erase_edges_device_impl(c->ctx, *in, d_erase, out); });
+}
+
+int mtg_boss_chunk_extend_device(mtg_boss_ctor *c, mtg_boss_device_chunk *dst, uint64_t dst_capacity_rows,
+                                 const mtg_boss_device_chunk *src) {
+    if (!c || !dst || !src || !dst->W || !dst->last || !src->W || !src->last || src->n < 1)
+        return bad_arguments("chunk_extend_device: bad arguments");
+    if (dst->k != src->k) return bad_arguments("chunk_extend_device: trying to concatenate incompatible graph chunks");
+    if ((dst->weights == nullptr) != (src->weights == nullptr))
+        return bad_arguments("chunk_extend_device: trying to concatenate weighted and unweighted blocks");
+    if (dst->n > dst_capacity_rows || src->n > dst_capacity_rows - dst->n + (dst->n ? 1 : 0))
+        return bad_arguments("chunk_extend_device: the destination's capacity is too small");
+    return dbg_device_call(c, [&] { chunk_extend_device_impl(c->ctx, dst, dst_capacity_rows, *src); });
 }
 
 int mtg_sdsl_write(const char *path, int kind, const void *data, uint64_t nbits) {

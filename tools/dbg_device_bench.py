@@ -5,8 +5,14 @@
 (b) mtg_boss_write_dbg_device on the chunk where it lies, with its device / copy / host split.
 Each path runs once after one warm-up, both write --mask-dummy files with the default suffix index,
 and the two file sets are compared byte for byte.  Prints one JSON line and writes it to --out.
-Set MTG_TRACE=1 to get the host remainder of (b) by container on stderr."""
+Set MTG_TRACE=1 to get the host remainder of (b) by container on stderr.
+
+--prune times `concatenate --clear-dummy` instead: the suffix chunks (--suffix-len) of a FASTA file are
+built on the GPU, concatenated, and pruned and written (c) by the host writer (prune=True) from the
+concatenated host chunk and (d) by mtg_boss_write_dbg_device_pruned from the same rows uploaded, in
+basic and canonical mode, with the same comparison."""
 import argparse
+import ctypes
 import filecmp
 import importlib
 import json
@@ -22,6 +28,81 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 
+def prune_main(args):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import seq_io  # tests/seq_io.py: the FASTA reader of the tests
+    boss = importlib.import_module("projects2014-metagenome_amd.boss")
+    if boss.device_count() < 1:
+        sys.exit("dbg_device_bench: no GPU (a measurement does not fall back)")
+    seqs = seq_io.read_sequences(args.fasta)
+    kb = args.k - 1
+    L = boss.lib()
+    parent = args.dir or ("/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir())
+    out_dir = tempfile.mkdtemp(prefix="mtg_dbg_bench_", dir=parent)
+    modes, ok = {}, True
+    try:
+        for name, both in (("basic", False), ("canonical", True)):
+            chunks = []
+            for suf in boss.generate_suffixes(args.suffix_len):
+                c = boss.IBOSSChunkConstructor.initialize(kb, both_strands=both, filter_suffix=suf)
+                c.add_sequences(seqs)
+                chunks.append(c.build_chunk())
+            cat = boss.concatenate(chunks)
+            n = len(cat.W)
+            writer = boss.IBOSSChunkConstructor.initialize(kb, both_strands=both)
+            dc = boss._DeviceChunk(k=kb, n=n)
+            ptrs = []
+            for field, arr in (("W", np.ascontiguousarray(cat.W, np.uint8)), ("last", np.ascontiguousarray(cat.last, np.uint8))):
+                d = L.mtg_device_alloc(0, n)
+                assert d and L.mtg_memcpy_h2d(d, arr.ctypes.data, n) == 0
+                ptrs.append(d)
+                setattr(dc, field, d)
+            dc.F = (ctypes.c_uint64 * 5)(*[int(f) for f in cat.F])
+            host_chunk = boss.Chunk(kb, cat.W, None, cat.F, last_words=boss.pack_last(cat.last))
+
+            def host_path(base):
+                t0 = time.perf_counter()
+                nv = host_chunk.write_dbg(base, canonical=both, mask_dummy=True, prune=True)
+                return nv, {"write_dbg_s": time.perf_counter() - t0}
+
+            def device_path(base):
+                t0 = time.perf_counter()
+                nv = writer.write_dbg_device(dc, base, canonical=both, prune=True)
+                split = dict(writer.last_dbg_timings)
+                split["total_s"] = time.perf_counter() - t0
+                split["n_erased"] = int(writer.last_dbg_erased)
+                return nv, split
+
+            host_path(os.path.join(out_dir, "warm_h"))
+            device_path(os.path.join(out_dir, "warm_d"))
+            nv_h, host = host_path(os.path.join(out_dir, "h"))
+            nv_d, dev = device_path(os.path.join(out_dir, "d"))
+            same = not os.path.exists(os.path.join(out_dir, "d.dbg.weights"))
+            for ext in (".dbg", ".edgemask"):
+                same = same and filecmp.cmp(os.path.join(out_dir, "h" + ext), os.path.join(out_dir, "d" + ext), shallow=False)
+            for d in ptrs:
+                L.mtg_device_free(d)
+            ok = ok and same and nv_h == nv_d
+            modes[name] = {"rows": n, "host_writer": host, "device_writer": dev,
+                           "ratio_host_over_device": host["write_dbg_s"] / dev["total_s"],
+                           "n_valid": int(nv_d), "n_valid_equal": bool(nv_h == nv_d), "bytes_equal": bool(same)}
+    finally:
+        shutil.rmtree(out_dir, ignore_errors=True)
+    res = {"workload": "%s: suffix chunks of length %d, DBG k = %d, concatenated, pruned and written"
+                       % (os.path.basename(args.fasta), args.suffix_len, args.k),
+           "directory": parent,
+           "protocol": "each path once after one warm-up; wall clock around calls that end synchronised; the "
+                       "host time excludes the copy of the chunk to the host, the device time the upload",
+           "modes": modes}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=10_000_000)
@@ -29,8 +110,15 @@ def main():
     ap.add_argument("--k", type=int, default=31, help="DBG k (BOSS k = k - 1)")
     ap.add_argument("--count-width", type=int, default=0)
     ap.add_argument("--dir", default=None, help="where the files go (default: a fresh directory on /dev/shm or $TMPDIR)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dbg_device_bench.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/dbg_device_bench.json, dbg_prune_bench.json with --prune")
+    ap.add_argument("--prune", action="store_true", help="time the pruned writers on concatenated suffix chunks")
+    ap.add_argument("--fasta", default=os.path.join(ROOT, "tests", "golden", "transcripts_1000.fa"))
+    ap.add_argument("--suffix-len", type=int, default=1)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "dbg_prune_bench.json" if args.prune else "dbg_device_bench.json")
+    if args.prune:
+        return prune_main(args)
 
     import torch
     import bench
