@@ -190,6 +190,29 @@ int mtg_boss_ctor_add_packed(mtg_boss_ctor *ctor, const char *data, const uint64
 int mtg_boss_ctor_add_fasta(mtg_boss_ctor *ctor, const char *path);
 
 /*
+ * Contigs with per-k-mer counts as input: the `--count-kmers` branch of parse_sequences
+ * (cli/parse_sequences.hpp:103-143) over read_extended_fasta_file_critical
+ * (seq_io/sequence_io.cpp:407-467), the pair `metagraph clean` / `transform --to-fasta` write.  Names as
+ * in the reference: base = path without a trailing ".gz" and then without ".fasta"; the sequences are
+ * base.fasta.gz and the counts base.kmer_counts.gz (a u32 k-mer length, then one u32 per k-mer of every
+ * record in file order); either file may be plain or gzip (by its magic bytes).  The reference cuts every
+ * record into its runs of equal counts and adds each run with its count; here the calling thread reads
+ * and inflates both files into pinned memory, and at build time the records are split on the device and
+ * the runs become (start, count) pairs over the unsegmented sequence (csrc/kmer_counts.hpp), staged
+ * behind the reads, the KMC records and the plain FASTA files.  Counts above the count width's maximum
+ * saturate as those of mtg_boss_ctor_add_sequences do.  Thread-safe; one thread per file.
+ * Refused here with MTG_ERR_ARGUMENT, nothing staged: a file that cannot be read, a counts file shorter
+ * than 4 bytes, counts for another k than the constructor's k + 1, a payload that is no multiple of 4
+ * bytes, FASTQ content, a constructor with bits_per_count == 0 (the reference takes this branch only
+ * under --count-kmers: use mtg_boss_ctor_add_fasta).  Refused by build_chunk[_dist] with
+ * MTG_ERR_ARGUMENT: a record shorter than k, fewer or more counts than the records have k-mers.
+ * A constructor with a filter_suffix returns MTG_ERR_UNSUPPORTED: on that route the reference pads every
+ * equal-count segment with '$' as a sequence of its own, which adds dummy edges per segment; that is not
+ * built.  Not covered either: the with_reverse flag (both strands' counts are the both_strands build).
+ */
+int mtg_boss_ctor_add_fasta_counts(mtg_boss_ctor *ctor, const char *path);
+
+/*
  * A KMC1 k-mer counter database (`<base>.kmc_pre` + `<base>.kmc_suf`; either name or the base) as
  * input: seq_io::read_kmers (seq_io/kmc_parser.cpp:27-62) + the build's KMC branch
  * (cli/parse_sequences.hpp:50-101).  Every k-mer with min_count <= count < max_count becomes a
@@ -218,6 +241,22 @@ typedef struct mtg_device_reads {
 int mtg_kmc_load_device(const char *kmc_path, uint64_t min_count, uint64_t max_count,
                         int call_both_from_canonical, int device_id, mtg_device_reads *out);
 void mtg_device_reads_free(mtg_device_reads *reads);
+
+/*
+ * The device step of mtg_boss_ctor_add_fasta_counts alone, for callers that hold everything in HBM: the
+ * record starts of a read buffer (record r = [d_record_starts[r], d_record_starts[r + 1] - 1), one
+ * separator byte after every record; n_records + 1 entries) and the records' k-mer counts (one per
+ * window, record after record: the counts file's payload) -> the runs of equal counts of
+ * cli/parse_sequences.hpp:120-138 as `out->read_starts` / `out->counts` / `out->n_reads`, exactly what
+ * mtg_boss_build_device takes as d_read_starts / d_counts / n_reads next to the same buffer.  out->seq
+ * stays NULL; free `out` with mtg_device_reads_free.  k is the DBG k (BOSS k + 1).  MTG_ERR_ARGUMENT: a
+ * record shorter than k ("Bad fasta file. Found sequence shorter than k-mer length"), fewer counts than
+ * windows ("Cannot read k-mer features") or more ("There are features left in extension unread").  Takes
+ * the constructor's mutex and runs on `stream` (NULL = its own) with its scratch, like the device writers.
+ */
+int mtg_kmer_counts_to_reads_device(mtg_boss_ctor *ctor, const uint64_t *d_record_starts /* n_records + 1 */,
+                                    uint64_t n_records, const uint32_t *d_kmer_counts, uint64_t n_counts,
+                                    unsigned k /* DBG k */, void *stream, mtg_device_reads *out);
 
 /*
  * The builder's own k-mer counter: counts the k-mers (k <= 32; canonical = KMC's canonical form,

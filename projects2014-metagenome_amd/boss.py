@@ -119,7 +119,8 @@ EXPORTS = ("mtg_boss_abi_version", "mtg_last_error", "mtg_boss_ctor_create",
            "mtg_device_reads_free", "mtg_kmc_write_device", "mtg_host_pool_bytes",
            "mtg_host_pool_trim", "mtg_comm_create_callbacks", "mtg_comm_local_held_ms",
            "mtg_boss_ctor_trim", "mtg_boss_write_dbg_device", "mtg_boss_write_dbg_device_pruned",
-           "mtg_boss_erase_edges_device", "mtg_boss_chunk_extend_device")
+           "mtg_boss_erase_edges_device", "mtg_boss_chunk_extend_device",
+           "mtg_boss_ctor_add_fasta_counts", "mtg_kmer_counts_to_reads_device")
 
 COMM_ID_BYTES = 128
 
@@ -214,6 +215,10 @@ def lib():
                                                   P(_DeviceChunk)]
         L.mtg_boss_chunk_extend_device.argtypes = [ctypes.c_void_p, P(_DeviceChunk), ctypes.c_uint64,
                                                    P(_DeviceChunk)]
+        L.mtg_boss_ctor_add_fasta_counts.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        L.mtg_kmer_counts_to_reads_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint,
+                                                      ctypes.c_void_p, P(_DeviceReads)]
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -453,6 +458,28 @@ class BOSSChunkConstructor:
             for f in [ex.submit(self.add_fasta, p) for p in paths]:
                 f.result()
 
+    def add_fasta_counts(self, path):
+        """Contigs with per-k-mer counts (X.fasta.gz + X.kmer_counts.gz; `path` is X, X.fasta or
+        X.fasta.gz): parse_sequences' --count-kmers branch (cli/parse_sequences.hpp:103-143); the runs
+        of equal counts are found on the device at build time (mtg_boss_ctor_add_fasta_counts)."""
+        _check(lib().mtg_boss_ctor_add_fasta_counts(self._h, os.fsencode(path)))
+
+    def add_fasta_counts_files(self, paths, threads=None):
+        """add_fasta_counts for every path, one host thread per file like add_fasta_files."""
+        from concurrent.futures import ThreadPoolExecutor
+        paths = list(paths)
+        with ThreadPoolExecutor(max_workers=threads or max(1, min(len(paths), os.cpu_count() or 1))) as ex:
+            for f in [ex.submit(self.add_fasta_counts, p) for p in paths]:
+                f.result()
+
+    def kmer_counts_to_reads(self, d_record_starts, n_records, d_kmer_counts, n_counts, k=None, stream=None):
+        """Device-resident record starts (n_records + 1) and per-k-mer counts -> the runs of equal
+        counts as a DeviceReads (read_starts, counts, n_reads; seq is None): what build_device takes
+        next to the same read buffer (mtg_kmer_counts_to_reads_device).  k is the DBG k (default:
+        this constructor's k + 1)."""
+        return DeviceReads._from_runs(self, d_record_starts, n_records, d_kmer_counts, n_counts,
+                                      self._k + 1 if k is None else k, stream)
+
     def add_kmc(self, kmc_path, min_count=1, max_count=2**32 - 1,
                 call_both_from_canonical=None):
         """KMC1 database input (cli/parse_sequences.hpp:50-101, seq_io/kmc_parser.cpp:27-62).
@@ -585,7 +612,8 @@ class BOSSConstructor(BOSSChunkConstructor):
 
 class DeviceReads:
     """A KMC1 database decoded into device memory (mtg_kmc_load_device): the read buffer, per-read
-    starts and counts that build_device takes, as add_kmc would decode them at build time."""
+    starts and counts that build_device takes, as add_kmc would decode them at build time.  Also
+    what BOSSChunkConstructor.kmer_counts_to_reads returns (starts and counts only, seq None)."""
 
     def __init__(self, kmc_path, min_count=1, max_count=2**32 - 1, call_both_from_canonical=False,
                  device_id=0):
@@ -593,6 +621,14 @@ class DeviceReads:
         _check(lib().mtg_kmc_load_device(os.fsencode(kmc_path), min_count, max_count,
                                          int(bool(call_both_from_canonical)), device_id,
                                          ctypes.byref(self._r)))
+
+    @classmethod
+    def _from_runs(cls, ctor, d_record_starts, n_records, d_kmer_counts, n_counts, k, stream):
+        self = cls.__new__(cls)
+        self._r = _DeviceReads()
+        _check(lib().mtg_kmer_counts_to_reads_device(ctor._h, d_record_starts, n_records, d_kmer_counts,
+                                                     n_counts, k, stream, ctypes.byref(self._r)))
+        return self
 
     seq = property(lambda self: self._r.seq)
     seq_len = property(lambda self: self._r.seq_len)

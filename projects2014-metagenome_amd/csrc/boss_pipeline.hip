@@ -43,6 +43,7 @@
 #include "sort_unique.hpp"
 #include "collect_stage.hpp"
 #include "dummy_stage.hpp"
+#include "kmer_counts.hpp"
 #include "chunk_host.hpp"
 
 namespace mtg {
@@ -3212,9 +3213,18 @@ struct mtg_boss_ctor {
     std::atomic<uint64_t> stage_ns{0};  // host time spent staging since the last build
     std::mutex fa_mu;
     std::vector<mtg::FastaInput> fasta;  // FASTA / FASTQ files, split into reads on the device
+    struct CountedFasta {                // contigs with per-k-mer counts (kmer_counts.hpp)
+        mtg::FastaInput fa, cf;          // X.fasta.gz and X.kmer_counts.gz (a u32 k, then the u32 counts)
+        uint64_t n_counts = 0;
+    };
+    std::vector<CountedFasta> counted;   // (under fa_mu)
     mtg::PinnedLanding land_w4, land_wn;  // where the 4-bit W and the narrowed weights land (chunk_host.hpp)
     ~mtg_boss_ctor() {
         for (auto &f : fasta) mtg::free_fasta(f);
+        for (auto &f : counted) {
+            mtg::free_fasta(f.fa);
+            mtg::free_fasta(f.cf);
+        }
     }
 };
 
@@ -3418,59 +3428,172 @@ int mtg_boss_ctor_add_fasta(mtg_boss_ctor *c, const char *path) {
     });
 }
 
-// the staged FASTA / FASTQ files -> reads appended to dseq at *seq_base (fasta.hpp); with
-// per-read counts (rstarts != nullptr) also their starts (count 1) from read index *read_base.
-// count_only: only sizes (*seq_base / *read_base advance by what the files will write).
-static void split_fasta_files(mtg_boss_ctor *c, uint8_t *dseq, uint64_t *seq_base, uint64_t *rstarts,
-                              uint32_t *rcounts, uint64_t *read_base, bool count_only) {
-    Ctx &x = c->ctx;
-    hipStream_t s = x.stream;
-    for (const FastaInput &f : c->fasta) {
+// utils::remove_suffix(file, ".gz", ".fasta") of the reference: each suffix once, in that order
+static std::string counted_base(std::string path) {
+    for (const char *suf : {".gz", ".fasta"}) {
+        const size_t n = std::strlen(suf);
+        if (path.size() >= n && path.compare(path.size() - n, n, suf) == 0) path.resize(path.size() - n);
+    }
+    return path;
+}
+
+int mtg_boss_ctor_add_fasta_counts(mtg_boss_ctor *c, const char *path) {
+    if (!c || !path) return bad_arguments();
+    if (!c->suffix.empty()) {
+        set_error("counted contigs on the suffix-filtered route are not supported: the reference pads every "
+                  "equal-count segment with '$' there");
+        return MTG_ERR_UNSUPPORTED;
+    }
+    if (!c->params.bits_per_count)
+        return bad_arguments("k-mer counts need a constructor with bits_per_count > 0 (--count-kmers); use "
+                             "mtg_boss_ctor_add_fasta otherwise");
+    return abi_call(MTG_ERR_ARGUMENT, [&] {
+        StageTimer t{c->stage_ns};
+        const std::string base = counted_base(path);
+        mtg_boss_ctor::CountedFasta in;
+        struct Guard {  // nothing stays pinned when a check refuses the pair
+            mtg_boss_ctor::CountedFasta *p;
+            ~Guard() {
+                if (p) {
+                    free_fasta(p->fa);
+                    free_fasta(p->cf);
+                }
+            }
+        } guard{&in};
+        in.fa = load_fasta_file(base + ".fasta.gz");
+        if (in.fa.fastq)
+            throw std::runtime_error("ERROR: " + in.fa.path + " holds FASTQ records: k-mer counts come with FASTA contigs");
+        in.cf = read_file_pinned(base + ".kmer_counts.gz");
+        if (in.cf.size < 4) throw std::runtime_error("ERROR: Cannot read from file " + in.cf.path);
+        uint32_t kmer_length;
+        std::memcpy(&kmer_length, in.cf.data, 4);
+        if (kmer_length != c->params.k + 1)
+            throw std::runtime_error("File " + std::string(path) + " contains counts for k-mers of length " +
+                                     std::to_string(kmer_length) + " but graph is constructed with k=" +
+                                     std::to_string(c->params.k + 1));
+        if ((in.cf.size - 4) % 4)
+            throw std::runtime_error("ERROR: Cannot read k-mer features: the counts of " + in.cf.path +
+                                     " are not a multiple of 4 bytes");
+        in.n_counts = (in.cf.size - 4) / 4;
+        std::lock_guard<std::mutex> lock(c->fa_mu);
+        c->counted.push_back(in);
+        guard.p = nullptr;
+        return MTG_OK;
+    });
+}
+
+// One staged FASTA / FASTQ file split on the device (fasta.hpp) in two steps: count() copies the file to
+// HBM and sizes its output (the kept bytes and the records), write() stores the reads at seq_base of dseq
+// and, with rstarts, the record starts (count 1) from read index read_base.  The workspace's FA_* slots
+// hold the state between the two, so one file is split at a time.
+struct FastaSplit {
+    const FastaInput &f;
+    uint64_t nt = 0, keep = 0, reads = 0;
+    uint8_t *raw = nullptr;
+    int64_t *prev = nullptr;
+    uint64_t *oa = nullptr, *ob = nullptr, *koff = nullptr;
+
+    void count(Ctx &x) {
+        hipStream_t s = x.stream;
         const uint64_t n = f.size;
-        const uint64_t nt = ceil_div(n, FA_TILE);
-        uint8_t *raw = (uint8_t *)x.ws.get(Workspace::FA_RAW, n + 64);
+        nt = ceil_div(n, FA_TILE);
+        raw = (uint8_t *)x.ws.get(Workspace::FA_RAW, n + 64);
         int64_t *tlast = (int64_t *)x.ws.get(Workspace::FA_TLAST, (nt + 1) * 8);
-        int64_t *prev = (int64_t *)x.ws.get(Workspace::FA_PREV, (nt + 1) * 8);
+        prev = (int64_t *)x.ws.get(Workspace::FA_PREV, (nt + 1) * 8);
         uint32_t *ta = (uint32_t *)x.ws.get(Workspace::FA_TA, (nt + 1) * 4);
         uint32_t *tb = (uint32_t *)x.ws.get(Workspace::FA_TB, (nt + 1) * 4);
-        uint64_t *oa = (uint64_t *)x.ws.get(Workspace::FA_OA, (nt + 1) * 8);
-        uint64_t *ob = (uint64_t *)x.ws.get(Workspace::FA_OB, (nt + 1) * 8);
+        oa = (uint64_t *)x.ws.get(Workspace::FA_OA, (nt + 1) * 8);
+        ob = (uint64_t *)x.ws.get(Workspace::FA_OB, (nt + 1) * 8);
         HIP_CHECK(hipMemcpyAsync(raw, f.data, n, hipMemcpyHostToDevice, s));
         fasta_stats_kernel<<<dim3((unsigned)nt), dim3(FA_BLOCK), 0, s>>>(raw, n, tlast, ta);
         HIP_CHECK(hipGetLastError());
         fasta_prefix_kernel<<<1, 1024, 0, s>>>(tlast, ta, nullptr, nt, prev, oa, nullptr);  // prev nl, lines
         HIP_CHECK(hipGetLastError());
-        const uint64_t fh = f.first_header;
         HIP_CHECK(hipMemsetAsync(&x.small->fasta_bad, 0, 4, s));
         fasta_split_kernel<false><<<dim3((unsigned)nt), dim3(FA_BLOCK), 0, s>>>(
-            raw, n, f.fastq ? 1 : 0, fh, prev, oa, ta, tb, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0,
+            raw, n, f.fastq ? 1 : 0, f.first_header, prev, oa, ta, tb, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0,
             f.lines_before, &x.small->fasta_bad);
         HIP_CHECK(hipGetLastError());
-        uint64_t *koff = (uint64_t *)x.ws.get(Workspace::FA_KOFF, (nt + 1) * 8);
+        koff = (uint64_t *)x.ws.get(Workspace::FA_KOFF, (nt + 1) * 8);
         fasta_prefix_kernel<<<1, 1024, 0, s>>>(nullptr, ta, tb, nt, nullptr, koff, ob);
         HIP_CHECK(hipGetLastError());
-        uint64_t tot[2];
         uint32_t bad = 0;
-        HIP_CHECK(hipMemcpyAsync(&tot[0], koff + nt, 8, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(&tot[1], ob + nt, 8, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(&keep, koff + nt, 8, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(&reads, ob + nt, 8, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipMemcpyAsync(&bad, &x.small->fasta_bad, 4, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         if (bad)
             throw std::runtime_error("ERROR: " + f.path + ": a FASTA sequence line starts with '+' (FASTQ quality in a "
                                      "FASTA record) -- not supported");
-        if (!count_only) {
-            // the line-number prefix `oa` is still valid: the second prefix wrote koff / ob
-            fasta_split_kernel<true><<<dim3((unsigned)nt), dim3(FA_BLOCK), 0, s>>>(
-                raw, n, f.fastq ? 1 : 0, fh, prev, oa, nullptr, nullptr, koff, ob, dseq, *seq_base, rstarts,
-                rcounts, *read_base, f.lines_before, nullptr);
-            HIP_CHECK(hipGetLastError());
-            const uint8_t sep = '$';  // the last record's separator
-            HIP_CHECK(hipMemcpyAsync(dseq + *seq_base + tot[0], &sep, 1, hipMemcpyHostToDevice, s));
-            HIP_CHECK(hipStreamSynchronize(s));  // the slots are reused by the next file
-        }
-        *seq_base += tot[0] + 1;
-        *read_base += tot[1];
     }
+
+    void write(Ctx &x, uint8_t *dseq, uint64_t seq_base, uint64_t *rstarts, uint32_t *rcounts, uint64_t read_base) {
+        hipStream_t s = x.stream;
+        // the line-number prefix `oa` is still valid: the second prefix wrote koff / ob
+        fasta_split_kernel<true><<<dim3((unsigned)nt), dim3(FA_BLOCK), 0, s>>>(
+            raw, f.size, f.fastq ? 1 : 0, f.first_header, prev, oa, nullptr, nullptr, koff, ob, dseq, seq_base, rstarts,
+            rcounts, read_base, f.lines_before, nullptr);
+        HIP_CHECK(hipGetLastError());
+        const uint8_t sep = '$';  // the last record's separator
+        HIP_CHECK(hipMemcpyAsync(dseq + seq_base + keep, &sep, 1, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));  // the slots are reused by the next file
+    }
+};
+
+// the staged FASTA / FASTQ files -> reads appended to dseq at *seq_base (fasta.hpp); with
+// per-read counts (rstarts != nullptr) also their starts (count 1) from read index *read_base.
+// count_only: only sizes (*seq_base / *read_base advance by what the files will write).
+static void split_fasta_files(mtg_boss_ctor *c, uint8_t *dseq, uint64_t *seq_base, uint64_t *rstarts,
+                              uint32_t *rcounts, uint64_t *read_base, bool count_only) {
+    for (const FastaInput &f : c->fasta) {
+        FastaSplit sp{f};
+        sp.count(c->ctx);
+        if (!count_only) sp.write(c->ctx, dseq, *seq_base, rstarts, rcounts, *read_base);
+        *seq_base += sp.keep + 1;
+        *read_base += sp.reads;
+    }
+}
+
+// One counted file behind the reads staged so far (kmer_counts.hpp): its records split into dseq at
+// *seq_base, and its runs of equal counts appended to the STARTS / RCOUNTS slots at *read_base.  The run
+// count sizes those arrays, so they grow here (keeping what the earlier inputs wrote).
+static void stage_counted_file(mtg_boss_ctor *c, const mtg_boss_ctor::CountedFasta &f, uint8_t *dseq,
+                               uint64_t *seq_base, uint64_t **dstarts, uint32_t **dcounts, uint64_t *read_base) {
+    Ctx &x = c->ctx;
+    hipStream_t s = x.stream;
+    if (!f.fa.size) {  // no bytes, no records
+        if (f.n_counts) throw KmerCountsError("ERROR: There are features left in extension unread");
+        return;
+    }
+    FastaSplit sp{f.fa};
+    sp.count(x);
+    const uint64_t n_rec = sp.reads;
+    uint64_t *rs = (uint64_t *)x.ws.get(Workspace::KC_RS, (n_rec + 1) * 8);
+    uint32_t *ones = (uint32_t *)x.ws.get(Workspace::KC_WCNT, (n_rec + 1) * 4);  // the split's count 1 per record: unused
+    sp.write(x, dseq, *seq_base, rs, ones, 0);
+    const uint64_t end = *seq_base + sp.keep + 1;  // one past the last record's separator
+    HIP_CHECK(hipMemcpyAsync(rs + n_rec, &end, 8, hipMemcpyHostToDevice, s));
+    uint32_t *cnt = (uint32_t *)x.ws.get(Workspace::KC_CNT, f.n_counts * 4);
+    if (f.n_counts) HIP_CHECK(hipMemcpyAsync(cnt, f.cf.data + 4, f.n_counts * 4, hipMemcpyHostToDevice, s));
+    uint64_t first = end;
+    if (n_rec) HIP_CHECK(hipMemcpyAsync(&first, rs, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    KmerCountRuns runs;
+    runs.rs = rs;
+    runs.n_rec = n_rec;
+    runs.counts = cnt;
+    runs.n_counts = f.n_counts;
+    runs.k = (uint32_t)c->params.k + 1;
+    const uint64_t n_runs = runs.plan(x, end - first);
+    if (n_runs) {
+        const uint64_t have = *read_base, want = have + n_runs;
+        *dstarts = (uint64_t *)x.ws.get(Workspace::STARTS, want * 8, *dstarts ? have * 8 : 0, s);
+        *dcounts = (uint32_t *)x.ws.get(Workspace::RCOUNTS, want * 4, *dcounts ? have * 4 : 0, s);
+        runs.write(x, *dstarts, *dcounts, have);
+        HIP_CHECK(hipStreamSynchronize(s));  // the slots are reused by the next file
+    }
+    *seq_base = end;
+    *read_base += n_runs;
 }
 
 // encode_filter_suffix_boss (boss_chunk_construct.cpp:935-945): '$' -> 0, else the BOSS code
@@ -3588,7 +3711,8 @@ static StagedInput stage_inputs(mtg_boss_ctor *c) {
     }
     uint64_t fa_bytes = 0, fa_reads = 0;
     for (const auto &f : c->fasta) fa_bytes += f.size + 1;  // split output <= raw bytes + a separator
-    const bool per_read_inputs = st.any_count_not_one() || kmc_reads;
+    for (const auto &f : c->counted) fa_bytes += f.fa.size + 1;
+    const bool per_read_inputs = st.any_count_not_one() || kmc_reads || !c->counted.empty();
     if (c->params.bits_per_count && per_read_inputs && !c->fasta.empty()) {
         uint64_t sb = 0;  // record counts first: the read-start arrays are sized by them
         split_fasta_files(c, nullptr, &sb, nullptr, nullptr, &fa_reads, true);
@@ -3650,9 +3774,11 @@ static StagedInput stage_inputs(mtg_boss_ctor *c) {
     }
     split_fasta_files(c, dseq, &seq_base, per_read ? dstarts : nullptr, per_read ? dcounts : nullptr, &read_base,
                       false);
+    // the counted files last: each one's runs grow the read arrays (a counted file needs bits_per_count)
+    for (const auto &f : c->counted) stage_counted_file(c, f, dseq, &seq_base, &dstarts, &dcounts, &read_base);
     HIP_CHECK(hipStreamSynchronize(s));
     const double input_ms = ms_since(t_input);
-    return {BuildInput{dseq, seq_base, dstarts, dcounts, per_read ? total_reads : 0}, h2d_ms, input_ms};
+    return {BuildInput{dseq, seq_base, dstarts, dcounts, dstarts ? read_base : 0}, h2d_ms, input_ms};
 }
 
 // the build's rows -> the chunk: W / packed last / weights in pinned blocks the chunk owns
@@ -3710,6 +3836,11 @@ static void finish_batch(mtg_boss_ctor *c, std::unique_lock<std::shared_mutex> &
     c->kmc.clear();
     for (auto &f : c->fasta) free_fasta(f);
     c->fasta.clear();
+    for (auto &f : c->counted) {
+        free_fasta(f.fa);
+        free_fasta(f.cf);
+    }
+    c->counted.clear();
     T.host_total_ms = ms_since(t_start);
 }
 
@@ -3728,7 +3859,13 @@ static int build_chunk_impl(mtg_boss_ctor *c, mtg::Comm *comm, mtg_boss_chunk *o
     std::memset(out, 0, sizeof(*out));
     const int rc = abi_call(MTG_ERR_DEVICE, [&] {
         HIP_CHECK(hipSetDevice(c->device));
-        const StagedInput si = stage_inputs(c);
+        StagedInput si;
+        try {
+            si = stage_inputs(c);
+        } catch (const KmerCountsError &e) {  // a counted file whose records and counts disagree
+            set_error(e.what());
+            return MTG_ERR_ARGUMENT;
+        }
         BuildOutput o{};
         dispatch_build(c, comm, si.in, comm == nullptr, &o);  // a single build with host arrays may spill
         const auto t_d2h = std::chrono::steady_clock::now();
@@ -3801,6 +3938,48 @@ void mtg_device_reads_free(mtg_device_reads *r) {
     r->read_starts = nullptr;
     r->counts = nullptr;
     r->seq_len = r->n_reads = 0;
+}
+
+int mtg_kmer_counts_to_reads_device(mtg_boss_ctor *c, const uint64_t *d_record_starts, uint64_t n_records,
+                                    const uint32_t *d_kmer_counts, uint64_t n_counts, unsigned k, void *stream,
+                                    mtg_device_reads *out) {
+    if (!c || !out || !d_record_starts || (n_counts && !d_kmer_counts) || k < 1 ||
+        ((uintptr_t)d_kmer_counts & 3) || ((uintptr_t)d_record_starts & 7))
+        return bad_arguments();
+    std::memset(out, 0, sizeof(*out));
+    out->device_id = c->device;
+    std::lock_guard<std::mutex> lock(c->mu);
+    hipStream_t saved = c->ctx.stream;
+    if (stream) c->ctx.stream = (hipStream_t)stream;
+    const int rc = abi_call(MTG_ERR_DEVICE, [&] {
+        try {
+            HIP_CHECK(hipSetDevice(c->device));
+            Ctx &x = c->ctx;
+            uint64_t first = 0, end = 0;
+            HIP_CHECK(hipMemcpyAsync(&first, d_record_starts, 8, hipMemcpyDeviceToHost, x.stream));
+            HIP_CHECK(hipMemcpyAsync(&end, d_record_starts + n_records, 8, hipMemcpyDeviceToHost, x.stream));
+            HIP_CHECK(hipStreamSynchronize(x.stream));
+            if (end < first) throw KmerCountsError("the record starts must ascend");
+            KmerCountRuns runs;
+            runs.rs = d_record_starts;
+            runs.n_rec = n_records;
+            runs.counts = d_kmer_counts;
+            runs.n_counts = n_counts;
+            runs.k = k;
+            out->n_reads = runs.plan(x, end - first);
+            HIP_CHECK(hipMalloc(&out->read_starts, std::max<uint64_t>(out->n_reads, 1) * 8));
+            HIP_CHECK(hipMalloc(&out->counts, std::max<uint64_t>(out->n_reads, 1) * 4));
+            runs.write(x, out->read_starts, out->counts, 0);
+            HIP_CHECK(hipStreamSynchronize(x.stream));
+            return MTG_OK;
+        } catch (const KmerCountsError &e) {
+            set_error(e.what());
+            return MTG_ERR_ARGUMENT;
+        }
+    });
+    c->ctx.stream = saved;
+    if (rc != MTG_OK) mtg_device_reads_free(out);
+    return rc;
 }
 
 int mtg_boss_build_device(mtg_boss_ctor *c, const uint8_t *d_seq, uint64_t seq_len,

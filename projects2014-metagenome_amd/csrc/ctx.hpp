@@ -31,7 +31,9 @@ class Workspace {
         SK_OWN, SK_TCNT, SK_TOFF, SK_WORDS, SK_LENS, SK_CNT, SK_RWORDS, SK_RLENS, SK_RCNT, SK_NW, SK_WOFF, SK_SEQ,
         SK_STARTS, SK_RID, CANON_IDX, SPEC_A, SPEC_B, SPEC_CAP, SPEC_CUR, GAP_BSTART, GAP_USTART, CANON, CANONC,
         FUSED_SEL, WN, SPEC_AC, SPEC_BC, SPEC1_CAPS, SPEC1_START, SPEC1_TV, QINDEX, DBITMAP, RC_L1START, RC_L1CUR, RC_TILEG,
-        KA2, ROUND_DELTA, XA2, XAC2, CA2, SPEC_MID_TV, NSLOTS
+        KA2, ROUND_DELTA, XA2, XAC2, CA2, SPEC_MID_TV,
+        // counted FASTA input (kmer_counts.hpp): record starts, counts payload, windows and run offsets
+        KC_RS, KC_CNT, KC_WCNT, KC_WOFF, KC_TCNT, KC_TOFF, NSLOTS
     };
     ~Workspace() {
         // every device block once, by its base (a slot or kept entry may be a piece of one: carve)
@@ -292,6 +294,7 @@ struct Small {  // one device word block, zeroed per use
     uint32_t spec_ovf;   // msd_partition_kernel: a speculative bucket overflowed
     uint32_t wbad;       // window_reads_kernel: the input is not one window per read
     unsigned long long wcursor;  // window_reads_kernel: keys written
+    uint32_t kc_bad;     // kc_windows_kernel: a record shorter than k (1) or too long (2)
     uint32_t error;
 };
 

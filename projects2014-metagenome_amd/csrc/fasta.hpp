@@ -54,7 +54,7 @@ struct FastaInput {
 };
 
 // read (and inflate) a file into pinned memory; throws with the reference's message style
-inline FastaInput load_fasta_file(const std::string &path) {
+inline FastaInput read_file_pinned(const std::string &path) {
     FastaInput in;
     in.path = path;
     uint64_t fsize = 0;
@@ -128,6 +128,14 @@ inline FastaInput load_fasta_file(const std::string &path) {
     }
     in.data = buf;
     in.size = size;
+    return in;
+}
+
+// the same, with the file's kind and its first header found
+inline FastaInput load_fasta_file(const std::string &path) {
+    FastaInput in = read_file_pinned(path);
+    char *buf = in.data;
+    const uint64_t size = in.size;
     uint64_t i = 0;
     while (i < size && (buf[i] == '\n' || buf[i] == '\r' || buf[i] == ' ')) ++i;
     in.fastq = i < size && buf[i] == '@';
