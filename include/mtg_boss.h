@@ -418,6 +418,70 @@ int mtg_boss_erase_edges_device(mtg_boss_ctor *ctor, const mtg_boss_device_chunk
 int mtg_boss_chunk_extend_device(mtg_boss_ctor *ctor, mtg_boss_device_chunk *dst, uint64_t dst_capacity_rows,
                                  const mtg_boss_device_chunk *src);
 
+/*
+ * The unitigs of a chunk in device memory with their k-mer counts: BOSS::call_unitigs (boss.cpp:2921-3015)
+ * over call_paths with split_to_unitigs (boss.cpp:2042-2236), filtered as `metagraph clean` filters them, all
+ * on the device (csrc/unitigs.hpp).  A k-mer is a real edge of the chunk (no source dummy, no sink); a unitig
+ * is a maximal chain of k-mers u -> v where v is the only k-mer after u and u the only k-mer before v; every
+ * k-mer lies in exactly one unitig.  A chain that closes on itself starts at its smallest row.  Records come
+ * in ascending row of their first k-mer, so the output is deterministic (the reference's order depends on its
+ * threads).  A unitig of m k-mers is a record of m + k chars (upper-case ACGT; k = the chunk's BOSS k) with
+ * its m weights in path order.
+ *   min_tip_size t: a unitig of fewer than t k-mers is dropped when it is a dead end, by call_unitigs' rule:
+ *     kept when its last k-mer has two or more successors, else kept when its first k-mer has two or more
+ *     predecessors, else dropped when the last has no successor, else dropped when the first has no
+ *     predecessor, else kept.
+ *   min_median_abundance a (is_unreliable_unitig, graph_cleaning.cpp:14-32): a unitig is dropped when more
+ *     than half of its k-mers weigh less than a.
+ * Both filters are evaluated on the unfiltered graph, in one pass.
+ * `seq` (records back to back, one '$' after each), `record_starts` (n_records + 1 entries) and
+ * `kmer_counts` are exactly what mtg_kmer_counts_to_reads_device (record starts + counts) and
+ * mtg_boss_build_device (the buffer) accept: build -> clean -> rebuild without leaving the device.  A chunk
+ * with no real edge gives zero records.  The chunk's arrays are only read; mutex, stream (NULL = the
+ * constructor's own) and scratch as for the device writers.  Free `out` with mtg_device_unitigs_free.
+ * The chunk must be a full construction or a pruned table: the unpruned concatenation of suffix chunks,
+ * whose redundant source dummies change the in-degrees, is not covered.  Not built: kmers_in_single_form
+ * (a canonical chunk yields the unitigs of both strands), call_sequences (contigs), --smoothing-window and
+ * the count-quantile slices of `clean`.
+ * MTG_ERR_ARGUMENT: NULL arguments, min_median_abundance > 1 on a chunk without weights.
+ * MTG_ERR_UNSUPPORTED: a chunk of 2^32 rows or more (the links are 32-bit).
+ */
+typedef struct mtg_unitig_params {
+    uint64_t min_tip_size;          /* 0 and 1: keep everything */
+    uint64_t min_median_abundance;  /* <= 1: off; > 1 needs weights, else MTG_ERR_ARGUMENT */
+} mtg_unitig_params;
+
+typedef struct mtg_device_unitigs {
+    uint8_t  *seq;            /* records back to back, one '$' after each; device */
+    uint64_t  seq_len;
+    uint64_t *record_starts;  /* n_records + 1 */
+    uint32_t *kmer_counts;    /* n_kmers entries or NULL (no weights) */
+    uint64_t  n_records, n_kmers;
+    uint64_t  n_dropped_records, n_dropped_kmers;   /* by the two filters */
+    int device_id;
+} mtg_device_unitigs;
+
+int mtg_boss_unitigs_device(mtg_boss_ctor *ctor, const mtg_boss_device_chunk *chunk,
+                            const mtg_unitig_params *params /* NULL = defaults: 1, 1 */, void *stream,
+                            mtg_device_unitigs *out);
+void mtg_device_unitigs_free(mtg_device_unitigs *unitigs);
+/* doubling rounds the ranking of the constructor's last mtg_boss_unitigs_device /
+   mtg_boss_write_unitigs_device call took (ceil(log2(longest unitig)) + 1, more with closed chains) */
+uint64_t mtg_boss_unitigs_last_rounds(const mtg_boss_ctor *ctor);
+
+/*
+ * The same unitigs written as the pair ExtendedFastaWriter writes (seq_io/sequence_io.cpp:91-183) and
+ * mtg_boss_ctor_add_fasta_counts reads: base = outbase without a trailing ".gz" and then without ".fasta";
+ * base.fasta.gz holds '>' + the record's 1-based number, a line end, the sequence on one line; with weights
+ * base.kmer_counts.gz holds a u32 k-mer length (k + 1), then the u32 counts in record order; both through
+ * zlib.  Without weights only the FASTA is written.  The three arrays go to pinned blocks of the host pool
+ * first.  `stats` (may be NULL) receives the counts, its pointers stay NULL.  Argument errors return before a
+ * file is opened; a file that cannot be written leaves none behind.
+ */
+int mtg_boss_write_unitigs_device(mtg_boss_ctor *ctor, const mtg_boss_device_chunk *chunk,
+                                  const mtg_unitig_params *params, const char *outbase,
+                                  mtg_device_unitigs *stats);
+
 /* One sdsl-lite container of the graph files written alone to `path` (the layout tests): kind 0
  * bit_vector_stat over `nbits` bits of `data`, 1 bit_vector_small (sd_vector or rrr_vector<63>,
  * whichever predict_size picks), 2 wt_huff<> over `nbits` bytes of `data`, 3 the sd_vector<> of the

@@ -51,6 +51,17 @@ class _DeviceReads(ctypes.Structure):
                 ("counts", ctypes.c_void_p), ("n_reads", ctypes.c_uint64), ("device_id", ctypes.c_int)]
 
 
+class _UnitigParams(ctypes.Structure):
+    _fields_ = [("min_tip_size", ctypes.c_uint64), ("min_median_abundance", ctypes.c_uint64)]
+
+
+class _DeviceUnitigs(ctypes.Structure):
+    _fields_ = [("seq", ctypes.c_void_p), ("seq_len", ctypes.c_uint64), ("record_starts", ctypes.c_void_p),
+                ("kmer_counts", ctypes.c_void_p), ("n_records", ctypes.c_uint64), ("n_kmers", ctypes.c_uint64),
+                ("n_dropped_records", ctypes.c_uint64), ("n_dropped_kmers", ctypes.c_uint64),
+                ("device_id", ctypes.c_int)]
+
+
 _ALLREDUCE_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t)
 _ALLGATHER_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                  ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t)
@@ -120,7 +131,9 @@ EXPORTS = ("mtg_boss_abi_version", "mtg_last_error", "mtg_boss_ctor_create",
            "mtg_host_pool_trim", "mtg_comm_create_callbacks", "mtg_comm_local_held_ms",
            "mtg_boss_ctor_trim", "mtg_boss_write_dbg_device", "mtg_boss_write_dbg_device_pruned",
            "mtg_boss_erase_edges_device", "mtg_boss_chunk_extend_device",
-           "mtg_boss_ctor_add_fasta_counts", "mtg_kmer_counts_to_reads_device")
+           "mtg_boss_ctor_add_fasta_counts", "mtg_kmer_counts_to_reads_device",
+           "mtg_boss_unitigs_device", "mtg_device_unitigs_free", "mtg_boss_write_unitigs_device",
+           "mtg_boss_unitigs_last_rounds")
 
 COMM_ID_BYTES = 128
 
@@ -219,6 +232,14 @@ def lib():
         L.mtg_kmer_counts_to_reads_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                                       ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint,
                                                       ctypes.c_void_p, P(_DeviceReads)]
+        L.mtg_boss_unitigs_device.argtypes = [ctypes.c_void_p, P(_DeviceChunk), P(_UnitigParams), ctypes.c_void_p,
+                                              P(_DeviceUnitigs)]
+        L.mtg_device_unitigs_free.argtypes = [P(_DeviceUnitigs)]
+        L.mtg_device_unitigs_free.restype = None
+        L.mtg_boss_write_unitigs_device.argtypes = [ctypes.c_void_p, P(_DeviceChunk), P(_UnitigParams),
+                                                    ctypes.c_char_p, P(_DeviceUnitigs)]
+        L.mtg_boss_unitigs_last_rounds.argtypes = [ctypes.c_void_p]
+        L.mtg_boss_unitigs_last_rounds.restype = ctypes.c_uint64
         for name in EXPORTS:
             getattr(L, name)
         _lib = L
@@ -558,6 +579,27 @@ class BOSSChunkConstructor:
         self.last_dbg_timings = t.as_dict()
         return nv.value
 
+    def unitigs_device(self, chunk, min_tip_size=1, min_median_abundance=1, stream=None):
+        """The unitigs of a device chunk with their k-mer counts, left in device memory
+        (mtg_boss_unitigs_device): BOSS::call_unitigs with `metagraph clean`'s two filters.  Returns a
+        DeviceUnitigs; its build_args() / counts_args() feed kmer_counts_to_reads and build_device."""
+        return DeviceUnitigs(self, chunk, min_tip_size, min_median_abundance, stream)
+
+    def write_unitigs_device(self, chunk, outbase, min_tip_size=1, min_median_abundance=1):
+        """The same unitigs as <base>.fasta.gz and, for a weighted chunk, <base>.kmer_counts.gz, the pair
+        add_fasta_counts reads (mtg_boss_write_unitigs_device).  Returns the statistics as a dict:
+        n_records, n_kmers, n_dropped_records, n_dropped_kmers, seq_len."""
+        p = _UnitigParams(int(min_tip_size), int(min_median_abundance))
+        u = _DeviceUnitigs()
+        _check(lib().mtg_boss_write_unitigs_device(self._h, ctypes.byref(chunk), ctypes.byref(p),
+                                                   os.fsencode(outbase), ctypes.byref(u)))
+        return {name: getattr(u, name) for name in ("n_records", "n_kmers", "n_dropped_records",
+                                                    "n_dropped_kmers", "seq_len")}
+
+    def unitigs_last_rounds(self):
+        """Doubling rounds the ranking of the last unitigs_device / write_unitigs_device call took."""
+        return lib().mtg_boss_unitigs_last_rounds(self._h)
+
     def erase_edges_device(self, chunk, d_erase, out):
         """BOSS::erase_edges on the device (mtg_boss_erase_edges_device): the rows of `chunk` whose byte of
         d_erase (a device pointer, one byte per row, row 0 must be 0) is 0 go to `out`, a _DeviceChunk
@@ -644,6 +686,43 @@ class DeviceReads:
         r, self._r = getattr(self, "_r", None), None
         if r is not None and _lib is not None:
             _lib.mtg_device_reads_free(ctypes.byref(r))
+
+
+class DeviceUnitigs:
+    """Unitigs of a device chunk in device memory (mtg_boss_unitigs_device): `seq` holds the records back
+    to back with one '$' after each, `record_starts` n_records + 1 offsets, `kmer_counts` one u32 per k-mer
+    in record order (None for an unweighted chunk).  Owns the arrays; they are freed with the object."""
+
+    def __init__(self, ctor, chunk, min_tip_size=1, min_median_abundance=1, stream=None):
+        self._u = _DeviceUnitigs()
+        p = _UnitigParams(int(min_tip_size), int(min_median_abundance))
+        _check(lib().mtg_boss_unitigs_device(ctor._h, ctypes.byref(chunk), ctypes.byref(p), stream,
+                                             ctypes.byref(self._u)))
+
+    seq = property(lambda self: self._u.seq)
+    seq_len = property(lambda self: self._u.seq_len)
+    record_starts = property(lambda self: self._u.record_starts)
+    kmer_counts = property(lambda self: self._u.kmer_counts)
+    n_records = property(lambda self: self._u.n_records)
+    n_kmers = property(lambda self: self._u.n_kmers)
+    n_dropped_records = property(lambda self: self._u.n_dropped_records)
+    n_dropped_kmers = property(lambda self: self._u.n_dropped_kmers)
+
+    def counts_args(self):
+        """(d_record_starts, n_records, d_kmer_counts, n_counts) for kmer_counts_to_reads."""
+        return self.record_starts, self.n_records, self.kmer_counts, self.n_kmers
+
+    def build_args(self, runs=None):
+        """(d_seq, seq_len, d_read_starts, d_counts, n_reads) for build_device: the buffer alone, or with
+        `runs` (what kmer_counts_to_reads returned for counts_args()) the counted build."""
+        if runs is None:
+            return self.seq, self.seq_len, None, None, 0
+        return self.seq, self.seq_len, runs.read_starts, runs.counts, runs.n_reads
+
+    def __del__(self):
+        u, self._u = getattr(self, "_u", None), None
+        if u is not None and _lib is not None:
+            _lib.mtg_device_unitigs_free(ctypes.byref(u))
 
 
 class Comm:

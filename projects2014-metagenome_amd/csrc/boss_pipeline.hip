@@ -3198,6 +3198,7 @@ static void run_dispatch(Ctx &c, Comm *comm, unsigned k, bool canonical, unsigne
 // the driver of the device graph writer: included here, after the pipelines, so that the kernels it is the
 // first to instantiate stay last in the code object and the pipelines' kernels keep their places in it
 #include "dbg_device_write.hpp"
+#include "unitigs_device.hpp"
 
 // ============================================================================ C ABI
 
@@ -3219,6 +3220,7 @@ struct mtg_boss_ctor {
     };
     std::vector<CountedFasta> counted;   // (under fa_mu)
     mtg::PinnedLanding land_w4, land_wn;  // where the 4-bit W and the narrowed weights land (chunk_host.hpp)
+    uint64_t unitig_rounds = 0;          // ranking rounds of the last unitig extraction (under mu)
     ~mtg_boss_ctor() {
         for (auto &f : fasta) mtg::free_fasta(f);
         for (auto &f : counted) {
@@ -4173,6 +4175,71 @@ int mtg_boss_chunk_extend_device(mtg_boss_ctor *c, mtg_boss_device_chunk *dst, u
     if (dst->n > dst_capacity_rows || src->n > dst_capacity_rows - dst->n + (dst->n ? 1 : 0))
         return bad_arguments("chunk_extend_device: the destination's capacity is too small");
     return dbg_device_call(c, [&] { chunk_extend_device_impl(c->ctx, dst, dst_capacity_rows, *src); });
+}
+
+// the checks the two unitig entries share, ahead of anything that touches the constructor
+static int unitig_arguments(const mtg_boss_ctor *c, const mtg_boss_device_chunk *chunk, const mtg_unitig_params *params,
+                            mtg_unitig_params *prm) {
+    if (!c || !chunk || !chunk->W || !chunk->last || chunk->n < 1) return bad_arguments("unitigs_device: bad arguments");
+    prm->min_tip_size = params ? params->min_tip_size : 1;
+    prm->min_median_abundance = params ? params->min_median_abundance : 1;
+    if (prm->min_median_abundance > 1 && !chunk->weights)
+        return bad_arguments("unitigs_device: min_median_abundance needs a chunk with weights");
+    if (chunk->n >= (1ull << 32)) {
+        set_error("unitigs_device: chunks of 2^32 rows or more are not supported (the links are 32-bit)");
+        return MTG_ERR_UNSUPPORTED;
+    }
+    return MTG_OK;
+}
+
+int mtg_boss_unitigs_device(mtg_boss_ctor *c, const mtg_boss_device_chunk *chunk, const mtg_unitig_params *params,
+                            void *stream, mtg_device_unitigs *out) {
+    mtg_unitig_params prm{};
+    if (!out) return bad_arguments("unitigs_device: bad arguments");
+    if (const int rc = unitig_arguments(c, chunk, params, &prm)) return rc;
+    std::memset(out, 0, sizeof(*out));
+    out->device_id = c->device;
+    hipStream_t saved = nullptr;
+    const int rc = dbg_device_call(c, [&] {
+        saved = c->ctx.stream;
+        struct Restore {
+            mtg_boss_ctor *c;
+            hipStream_t s;
+            ~Restore() { c->ctx.stream = s; }
+        } restore{c, saved};
+        if (stream) c->ctx.stream = (hipStream_t)stream;
+        UnitigRun run;
+        unitigs_device_impl(c->ctx, *chunk, prm, out, &run);
+        c->unitig_rounds = run.rank_rounds;
+    });
+    if (rc != MTG_OK) mtg_device_unitigs_free(out);
+    return rc;
+}
+
+void mtg_device_unitigs_free(mtg_device_unitigs *u) {
+    if (!u) return;
+    free_unitigs(u);
+    u->seq_len = u->n_records = u->n_kmers = 0;
+}
+
+uint64_t mtg_boss_unitigs_last_rounds(const mtg_boss_ctor *c) { return c ? c->unitig_rounds : 0; }
+
+int mtg_boss_write_unitigs_device(mtg_boss_ctor *c, const mtg_boss_device_chunk *chunk, const mtg_unitig_params *params,
+                                  const char *outbase, mtg_device_unitigs *stats) {
+    mtg_unitig_params prm{};
+    if (!outbase) return bad_arguments("unitigs_device: bad arguments");
+    if (const int rc = unitig_arguments(c, chunk, params, &prm)) return rc;
+    mtg_device_unitigs u{};
+    u.device_id = c->device;
+    const int rc = dbg_device_call(c, [&] {
+        UnitigRun run;
+        unitigs_device_impl(c->ctx, *chunk, prm, &u, &run);
+        c->unitig_rounds = run.rank_rounds;
+        write_unitigs_files(c->ctx, u, chunk->k + 1, counted_base(outbase), chunk->weights != nullptr);
+    });
+    free_unitigs(&u);
+    if (rc == MTG_OK && stats) *stats = u;
+    return rc;
 }
 
 int mtg_sdsl_write(const char *path, int kind, const void *data, uint64_t nbits) {

@@ -433,6 +433,39 @@ struct Nav {
         return true;
     }
     __device__ uint64_t fwd(uint64_t i, uint8_t c) const { return select_last(NF[c] + rank_W(i, c)); }
+    // the last char of row i's node: the largest c whose block of nodes starts before the node's rank
+    __device__ uint8_t node_last_char(uint64_t i) const {
+        if (i == 0) return 0;
+        const uint64_t node = rank_last(i - 1) + 1;
+        uint8_t c = 0;
+#pragma unroll
+        for (uint8_t s = 1; s < 5; ++s) c = NF[s] < node ? s : c;
+        return c;
+    }
+    // the row of the q-th plain c of W[1..] (rank_W's inverse): a search of the directory, then the block's
+    // rows; 0 when there is none
+    __device__ uint64_t select_W(uint64_t q, uint8_t c) const {
+        if (q == 0) return 0;
+        if (c == 0) ++q;  // row 0
+        uint64_t lo = 0, hi = nw;  // last block with wrank[c][b] < q
+        while (hi - lo > 1) {
+            const uint64_t mid = (lo + hi) / 2;
+            if (wrank[c][mid] < q) lo = mid; else hi = mid;
+        }
+        uint64_t r = q - wrank[c][lo];
+        const uint64_t end = 64 * lo + 64 < n ? 64 * lo + 64 : n;
+        for (uint64_t p = 64 * lo; p < end; ++p)
+            if (W[p] == c && --r == 0) return p;
+        return 0;
+    }
+    // BOSS::bwd: the plain edge into row i's node
+    __device__ uint64_t bwd(uint64_t i) const {
+        if (i == 0) return 0;
+        if (i >= n) i = n - 1;
+        const uint64_t node = rank_last(i - 1) + 1;
+        const uint8_t c = node_last_char(i);
+        return node > NF[c] ? select_W(node - NF[c], c) : 0;
+    }
 };
 
 struct FVec {

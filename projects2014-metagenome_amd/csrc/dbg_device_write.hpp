@@ -102,6 +102,39 @@ dbgdev::Nav build_nav(DevScratch &dev, hipStream_t s, const uint8_t *W, const ui
     return nav;
 }
 
+// The level-synchronous walk of the source-dummy tree (mark_all_dummy_edges): walked[i] (n zeroed bytes) = 1
+// for every row of a node that holds a '$'.  d_root: select_last(1) on the device (build_nav's sixth word);
+// h_count: one pinned word.  One host synchronisation per level; needs n > 1.
+void walk_source_dummies(DevScratch &dev, hipStream_t s, const dbgdev::Nav &nav, const uint64_t *d_root,
+                         uint64_t *h_count, uint8_t *walked, const char *who) {
+    using namespace dbgdev;
+    const uint64_t n = nav.n, k = nav.k;
+    DevScratch::Buf *fb[2] = {dev.make(), dev.make()}, *cb = dev.make(), *sb = dev.make(), *tb = dev.make();
+    uint64_t *cur = DevScratch::ensure<uint64_t>(fb[0], 1);
+    HIP_CHECK(hipMemcpyAsync(cur, d_root, 8, hipMemcpyDeviceToDevice, s));
+    uint64_t m = 1;
+    for (uint64_t depth = 0; depth < k && m; ++depth) {
+        const bool expand = depth + 1 < k;
+        uint32_t *cnt = DevScratch::ensure<uint32_t>(cb, m);
+        mask_count_kernel<<<dim3(dbg_grid(m)), dim3(kThreads), 0, s>>>(nav, cur, m, expand ? 1 : 0, cnt, walked);
+        HIP_CHECK(hipGetLastError());
+        if (!expand) break;
+        uint64_t *sc = DevScratch::ensure<uint64_t>(sb, m + 1);
+        exclusive_scan(cnt, m, sc, DevScratch::ensure<uint64_t>(tb, ceil_div(m, kScanTile) + 1), s);
+        HIP_CHECK(hipMemcpyAsync(h_count, sc + m, 8, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        const uint64_t next_m = *h_count;
+        if (next_m > n)
+            throw DbgArgumentError(std::string(who) + ": the arrays are no BOSS table (the source-dummy tree outgrows the rows)");
+        if (!next_m) break;
+        uint64_t *next = DevScratch::ensure<uint64_t>(fb[(depth + 1) & 1], next_m);
+        mask_expand_kernel<<<dim3(dbg_grid(m)), dim3(kThreads), 0, s>>>(nav, cur, m, sc, next, next_m);
+        HIP_CHECK(hipGetLastError());
+        cur = next;
+        m = next_m;
+    }
+}
+
 // The files from any device (W, last, n, F).  `flagged` (may be null): the mask's source-dummy flags, one
 // byte per row, already computed (the pruned path); without it mask_dummy walks the source-dummy tree
 // here.  pre_device_ms: device time the caller spent before this call, added to the timings.
@@ -257,31 +290,8 @@ uint64_t write_dbg_device_stages(Ctx &ctx, const mtg_boss_device_chunk &ch, unsi
             HIP_CHECK(hipMemsetAsync(walked, 0, n, s));
             flagged = walked;
         }
-        if (walked && n > 1) {
-            DevScratch::Buf *fb[2] = {dev.make(), dev.make()}, *cb = dev.make(), *sb = dev.make();
-            uint64_t *cur = DevScratch::ensure<uint64_t>(fb[0], 1);
-            HIP_CHECK(hipMemcpyAsync(cur, d_small + S_NAV + 5, 8, hipMemcpyDeviceToDevice, s));
-            uint64_t m = 1;
-            for (uint64_t depth = 0; depth < k && m; ++depth) {
-                const bool expand = depth + 1 < k;
-                uint32_t *cnt = DevScratch::ensure<uint32_t>(cb, m);
-                mask_count_kernel<<<dim3(dbg_grid(m)), dim3(kThreads), 0, s>>>(nav, cur, m, expand ? 1 : 0, cnt, walked);
-                HIP_CHECK(hipGetLastError());
-                if (!expand) break;
-                uint64_t *sc = DevScratch::ensure<uint64_t>(sb, m + 1);
-                exclusive_scan(cnt, m, sc, scan_tmp(m), s);
-                HIP_CHECK(hipMemcpyAsync(h_small + S_COUNT, sc + m, 8, hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                const uint64_t next_m = h_small[S_COUNT];
-                if (next_m > n) throw DbgArgumentError("write_dbg_device: the arrays are no BOSS table (the source-dummy tree outgrows the rows)");
-                if (!next_m) break;
-                uint64_t *next = DevScratch::ensure<uint64_t>(fb[(depth + 1) & 1], next_m);
-                mask_expand_kernel<<<dim3(dbg_grid(m)), dim3(kThreads), 0, s>>>(nav, cur, m, sc, next, next_m);
-                HIP_CHECK(hipGetLastError());
-                cur = next;
-                m = next_m;
-            }
-        }
+        if (walked && n > 1)
+            walk_source_dummies(dev, s, nav, d_small + S_NAV + 5, h_small + S_COUNT, walked, "write_dbg_device");
         maskw = dev.take<uint64_t>(nw);
         mask_pack_kernel<<<dim3(dbg_grid(nw)), dim3(kThreads), 0, s>>>(ch.W, flagged, n, nw, maskw,
                                                                     (unsigned long long *)(d_small + S_NVALID));

@@ -10,7 +10,10 @@ Set MTG_TRACE=1 to get the host remainder of (b) by container on stderr.
 --prune times `concatenate --clear-dummy` instead: the suffix chunks (--suffix-len) of a FASTA file are
 built on the GPU, concatenated, and pruned and written (c) by the host writer (prune=True) from the
 concatenated host chunk and (d) by mtg_boss_write_dbg_device_pruned from the same rows uploaded, in
-basic and canonical mode, with the same comparison."""
+basic and canonical mode, with the same comparison.
+
+--unitigs times mtg_boss_unitigs_device on the workload's counted chunk (events on the call's stream), reports
+its ranking rounds, records and k-mers, and times the rebuild from its output (profiles/unitigs_bench.json)."""
 import argparse
 import ctypes
 import filecmp
@@ -103,6 +106,60 @@ def prune_main(args):
     return 0 if ok else 1
 
 
+def unitigs_main(args):
+    """build -> unitigs with counts -> rebuild, all on the device: one sample after one warm-up"""
+    import torch
+    import bench
+    boss = importlib.import_module("projects2014-metagenome_amd.boss")
+    if not torch.cuda.is_available():
+        sys.exit("dbg_device_bench: no GPU (a measurement does not fall back)")
+    device = torch.device("cuda", 0)
+    torch.cuda.set_device(device)
+    seq = bench.make_reads_device(torch, args.reads, args.read_len, 1000, "genome", 10.0, device)
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    kb, width = args.k - 1, args.count_width or 8
+    ctor = boss.IBOSSChunkConstructor.initialize(kb, both_strands=True, bits_per_count=width)
+    dc = ctor.build_device(seq.data_ptr(), seq.numel())
+    build_ms = ctor.timings().total_ms
+    stream = torch.cuda.Stream(device)
+    rebuild = boss.IBOSSChunkConstructor.initialize(kb, both_strands=False, bits_per_count=width)
+
+    def once():
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record(stream)
+        u = ctor.unitigs_device(dc, stream=stream.cuda_stream)
+        ev[1].record(stream)
+        ev[1].synchronize()
+        t0 = time.perf_counter()
+        runs = rebuild.kmer_counts_to_reads(*u.counts_args())
+        dc2 = rebuild.build_device(*u.build_args(runs))
+        wall = time.perf_counter() - t0
+        return {"unitigs_device_ms": ev[0].elapsed_time(ev[1]), "ranking_rounds": int(ctor.unitigs_last_rounds()),
+                "records": int(u.n_records), "kmers": int(u.n_kmers), "seq_bytes": int(u.seq_len),
+                "rebuild_wall_s": wall, "rebuild_device_ms": rebuild.timings().total_ms,
+                "rebuilt_rows": int(dc2.n), "rebuilt_real": int(dc2.n_real)}
+
+    once()
+    sample = once()
+    ok = sample["kmers"] == int(dc.n_real) == sample["rebuilt_real"]
+    res = {"workload": "configs[1] generator: %d reads of %d bp, DBG k = %d, canonical, count width %d"
+                       % (args.reads, args.read_len, args.k, width),
+           "gpu": torch.cuda.get_device_name(0), "rows": int(dc.n), "real_edges": int(dc.n_real),
+           "build_device_ms": build_ms,
+           "protocol": "one sample after one warm-up; unitigs_device_ms between events on the call's stream (the "
+                       "call's host synchronisations included); the rebuild is a basic-mode counted build of the "
+                       "unitigs of both strands",
+           "unitigs": sample, "kmers_equal": bool(ok)}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=10_000_000)
@@ -114,11 +171,16 @@ def main():
     ap.add_argument("--prune", action="store_true", help="time the pruned writers on concatenated suffix chunks")
     ap.add_argument("--fasta", default=os.path.join(ROOT, "tests", "golden", "transcripts_1000.fa"))
     ap.add_argument("--suffix-len", type=int, default=1)
+    ap.add_argument("--unitigs", action="store_true",
+                    help="time mtg_boss_unitigs_device on the counted chunk and the rebuild from its output")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "dbg_prune_bench.json" if args.prune else "dbg_device_bench.json")
+        name = "dbg_prune_bench.json" if args.prune else "unitigs_bench.json" if args.unitigs else "dbg_device_bench.json"
+        args.out = os.path.join(ROOT, "profiles", name)
     if args.prune:
         return prune_main(args)
+    if args.unitigs:
+        return unitigs_main(args)
 
     import torch
     import bench
