@@ -253,6 +253,8 @@ void mtg_device_reads_free(mtg_device_reads *reads);
  * record shorter than k ("Bad fasta file. Found sequence shorter than k-mer length"), fewer counts than
  * windows ("Cannot read k-mer features") or more ("There are features left in extension unread").  Takes
  * the constructor's mutex and runs on `stream` (NULL = its own) with its scratch, like the device writers.
+ * On return the call has synchronised `stream` (n_reads is a host value), the two arrays are complete, and
+ * the constructor's own stream is restored whatever the return code.
  */
 int mtg_kmer_counts_to_reads_device(mtg_boss_ctor *ctor, const uint64_t *d_record_starts /* n_records + 1 */,
                                     uint64_t n_records, const uint32_t *d_kmer_counts, uint64_t n_counts,
@@ -279,6 +281,8 @@ void mtg_boss_chunk_free(mtg_boss_chunk *chunk);
  * byte outside {A,C,G,T,U,a,c,g,t,u} (so no k-mer spans two reads).  d_read_starts/d_counts
  * (both NULL, or n_reads entries) give per-read counts for --count-kmers.  `stream` is a
  * hipStream_t (NULL = the constructor's own stream).  Arrays stay in device memory.
+ * On return the call has synchronised `stream` (n, F and the totals are host values), the arrays are
+ * complete, and the constructor's own stream is restored whatever the return code.
  */
 int mtg_boss_build_device(mtg_boss_ctor *ctor, const uint8_t *d_seq, uint64_t seq_len,
                           const uint64_t *d_read_starts, const uint32_t *d_counts,
@@ -439,6 +443,8 @@ int mtg_boss_chunk_extend_device(mtg_boss_ctor *ctor, mtg_boss_device_chunk *dst
  * mtg_boss_build_device (the buffer) accept: build -> clean -> rebuild without leaving the device.  A chunk
  * with no real edge gives zero records.  The chunk's arrays are only read; mutex, stream (NULL = the
  * constructor's own) and scratch as for the device writers.  Free `out` with mtg_device_unitigs_free.
+ * On return the call has synchronised `stream` (the record and k-mer totals are host values), the three
+ * arrays are complete, and the constructor's own stream is restored whatever the return code.
  * The chunk must be a full construction or a pruned table: the unpruned concatenation of suffix chunks,
  * whose redundant source dummies change the in-degrees, is not covered.  Not built: kmers_in_single_form
  * (a canonical chunk yields the unitigs of both strands), call_sequences (contigs), --smoothing-window and
