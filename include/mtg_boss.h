@@ -156,6 +156,12 @@ typedef struct mtg_boss_timings {
                                     exchange 1 in flight under the owner sort of the previous piece) */
     uint64_t coresident;         /* multi-GPU: ranks sharing this rank's GPU (same host name and PCI bus id);
                                     they split its free HBM when planning rounds */
+    uint64_t rc_spec_l1;         /* the rc sort's level 1 fused with the rc map: 1 its buckets were sized from a
+                                    sample of the canonical set, 2 one of them overflowed and the exact
+                                    histogram pass ran instead, 0 neither (not fused, or MTG_RC_SPEC=0).
+                                    Appended like the fields before it, with MTG_BOSS_ABI_VERSION unchanged:
+                                    mtg_boss_last_timings writes sizeof(mtg_boss_timings) of this header, so a
+                                    caller must be compiled against the header of the library it loads */
 } mtg_boss_timings;
 
 int mtg_boss_abi_version(void);

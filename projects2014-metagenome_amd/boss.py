@@ -100,7 +100,8 @@ class Timings(ctypes.Structure):
                [(name, ctypes.c_uint64) for name in ("spec_levels", "spec_fine_levels", "spec_fallbacks",
                                                       "collect_mode", "sent_bytes", "spec_l1",
                                                       "cached_bytes")] + \
-               [("exchange_hidden_ms", ctypes.c_double), ("coresident", ctypes.c_uint64)]
+               [("exchange_hidden_ms", ctypes.c_double), ("coresident", ctypes.c_uint64),
+                ("rc_spec_l1", ctypes.c_uint64)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}

@@ -460,19 +460,22 @@ __global__ __launch_bounds__(256) void rc_map_kernel(const Key<L> *__restrict__ 
 
 // rc_map_kernel over a canonical set left in its speculative buckets (BuildState::gap in ctx.hpp):
 // bucket g's keys keys[bstart[g] ..) map to rc_out[ustart[g] .. ustart[g + 1]), one wave per bucket,
-// 4 loads in flight per lane
+// 4 loads in flight per lane.  gstride > 1 (the histogram alone, rc_out == nullptr): a sample -- every
+// gstride-th canonical bucket only (the rc sort's level-1 digit is the complement of a key's last
+// characters, close to independent of the key's place in canonical order)
 template <int L>
 __global__ __launch_bounds__(256) void rc_map_gapped_kernel(const Key<L> *__restrict__ keys,
                                                             const uint64_t *__restrict__ bstart,
                                                             const uint64_t *__restrict__ ustart, uint64_t nb,
                                                             Key<L> *__restrict__ rc_out, unsigned K,
-                                                            uint32_t *__restrict__ hist, unsigned hist_bits) {
+                                                            uint32_t *__restrict__ hist, unsigned hist_bits,
+                                                            uint32_t gstride = 1) {
     __shared__ uint32_t s_hist[512];
     if (hist_bits)
         for (uint32_t i = threadIdx.x; i < (1u << hist_bits); i += 256) s_hist[i] = 0;
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    for (uint64_t g = (uint64_t)blockIdx.x * 4 + wid; g < nb; g += (uint64_t)gridDim.x * 4) {
+    for (uint64_t g = ((uint64_t)blockIdx.x * 4 + wid) * gstride; g < nb; g += (uint64_t)gridDim.x * 4 * gstride) {
         const uint64_t src = bstart[g], dst = ustart[g], m = ustart[g + 1] - dst;
         for (uint64_t i0 = lane; i0 < m; i0 += 256) {
             Key<L> x[4];
@@ -528,11 +531,26 @@ __global__ __launch_bounds__(256) void rc_tile_bucket_kernel(const uint64_t *__r
     for (uint64_t t = (a + tile - 1) / tile; t * tile < e; ++t) tile_g[t] = g;
 }
 
+// rc_partition_gapped_kernel's level-1 buckets for tile_scatter.hpp: one cursor per bucket; exact buckets
+// (bend == nullptr: the full histogram pass counted these keys) or speculative ones sized from a sample,
+// bucket i ending at bend[i] and none past `limit`, the keys the output array holds
+struct RcLevel1Buckets {
+    const unsigned long long *bend;
+    unsigned long long limit;
+    __device__ __forceinline__ size_t cursor(uint32_t i) const { return i; }
+    __device__ __forceinline__ bool checked() const { return bend != nullptr; }
+    __device__ __forceinline__ unsigned long long end(uint32_t i, size_t) const { return min(bend[i], limit); }
+};
+
 template <int L>
 __global__ __launch_bounds__(512) void rc_partition_gapped_kernel(
     const Key<L> *__restrict__ keys, const uint64_t *__restrict__ bstart, const uint64_t *__restrict__ ustart,
     const uint64_t *__restrict__ tile_g, uint64_t nb, uint64_t U, unsigned K, unsigned hb,
-    unsigned long long *__restrict__ cursor, Key<L> *__restrict__ out) {
+    unsigned long long *__restrict__ cursor, Key<L> *__restrict__ out,
+    const unsigned long long *__restrict__ bend = nullptr, unsigned long long limit = 0,
+    uint32_t *__restrict__ povf = nullptr) {
+    // bend, limit, povf (speculative buckets; tile_scatter.hpp): a run that would pass its bucket's end is
+    // not written and *povf tells the host, which then runs the exact histogram pass and this kernel again
     using T = RcPartTraits<L>;
     constexpr int BLOCK = T::BLOCK, ITEMS = T::ITEMS, TILE = T::TILE, GS = T::GS, PER = T::NBM / BLOCK > 0 ? T::NBM / BLOCK : 1;
     __shared__ Key<L> s_keys[TILE];
@@ -633,15 +651,16 @@ __global__ __launch_bounds__(512) void rc_partition_gapped_kernel(
         r[j] = atomicAdd(&s_cnt[bucket_of(k[j])], 1u);
     }
     __syncthreads();
-    // tile_scatter.hpp; one cursor per level-1 bucket and no ends (the histogram pass counted these keys)
-    const TileRuns<PER> runs = tile_reserve_runs<BLOCK, PER, false>(s_cnt, s_loff, s_scan, nbk, cursor, PlainBuckets{});
+    // tile_scatter.hpp; one cursor per level-1 bucket, ends only where the buckets are speculative
+    const RcLevel1Buckets at{bend, limit};
+    const TileRuns<PER> runs = tile_reserve_runs<BLOCK, PER, false>(s_cnt, s_loff, s_scan, nbk, cursor, at);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j)
         if (r[j] != 0xFFFFFFFFu) s_keys[s_loff[bucket_of(k[j])] + r[j]] = k[j];
-    tile_publish_runs(runs, nbk, PlainBuckets{}, s_gbase);
+    tile_publish_runs(runs, nbk, at, s_gbase, [=] { *povf = 1u; });
     __syncthreads();
-    tile_write_runs<BLOCK>(s_keys, s_loff, s_gbase, runs.total, PlainBuckets{}, bucket_of,
+    tile_write_runs<BLOCK>(s_keys, s_loff, s_gbase, runs.total, at, bucket_of,
                            [=](uint64_t o, const Key<L> &key, uint32_t) { out[o] = key; });
 }
 

@@ -912,6 +912,71 @@ static bool collect_rounds_fused(Ctx &c, unsigned K, bool canonical, uint32_t cm
     return true;
 }
 
+// The fused rc partition (rc_partition_gapped_kernel) without its exact histogram pass, which read the whole
+// canonical set for 2^hb counters (0.38 ms at configs[1]): the level-1 buckets are sized from the rc keys of
+// every 8th canonical bucket with the speculative levels' slack (spec_caps_kernel: 1.2 n + 512 keys, rounded
+// up to whole level-2 tiles), the partition checks every run against its bucket's end, and the padded result
+// goes to the rc sort as the fused K1's speculative level-1 layout does (*pad: tile t holds keys in its
+// first tv[t] positions; hist1 = the exact counts, from the cursors).  The buckets live in RC_ALT, sized
+// before their total is known: 1.2 U + 512 keys and a tile a bucket, +5 % -- no bucket ends past that
+// (the kernel's `limit`), and a total past it counts as an overflow.  False: it does not fit (nothing
+// launched) or a bucket overflowed (rc_hist zeroed again); the caller runs the exact pass.
+template <int L2>
+static bool rc_level1_spec(Ctx &c, unsigned K, uint64_t U, uint32_t *rc_hist, unsigned hb, const uint64_t *tile_g,
+                           Key<L2> **keys_out, PaddedLayout *pad) {
+    constexpr uint32_t SS = 8, T2 = MsdTraits<L2>::TILE;
+    const GappedSet &gap = c.build.gap;
+    const uint64_t nbk = 1ull << hb, tiles = ceil_div(U, RcPartTraits<L2>::TILE);
+    const uint64_t limit = ((uint64_t)(1.2 * 1.05 * (double)U) + (512 + T2) * nbk + 65536) / T2 * T2;
+    const uint64_t need = limit * sizeof(Key<L2>), have = c.ws.held_slot(Workspace::RC_ALT);
+    if (have < need && (double)need > 0.9 * (double)c.ws.free_bytes() + (double)have) return false;
+    Key<L2> *dst = (Key<L2> *)c.ws.get(Workspace::RC_ALT, need);
+    const uint64_t ntv = limit / T2;
+    uint32_t *tv = (uint32_t *)c.ws.get(Workspace::SPEC_MID_TV, ntv * 4);
+    uint32_t *cap = (uint32_t *)c.ws.get(Workspace::SPEC_CAP, nbk * 4);
+    // (the starts, their total in st[nbk], and behind it the partition's overflow word: one read for both)
+    uint64_t *st = (uint64_t *)c.ws.get(Workspace::RC_L1START, (nbk + 2) * 8);
+    uint32_t *ovf = (uint32_t *)(st + nbk + 1);
+    auto *cur = (unsigned long long *)c.ws.get(Workspace::RC_L1CUR, nbk * 8);
+    rc_map_gapped_kernel<L2><<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(ceil_div(gap.nb, SS), 16), 16384))),
+                               dim3(256), 0, c.stream>>>((const Key<L2> *)gap.keys, gap.bstart, gap.ustart, gap.nb, nullptr, K,
+                                                         rc_hist, hb, SS);
+    HIP_CHECK(hipGetLastError());
+    spec_caps_kernel<<<dim3((unsigned)ceil_div(nbk, 256)), dim3(256), 0, c.stream>>>(rc_hist, nbk, SS, cap, c.knobs.rc_spec == 2,
+                                                                                     0, nbk, T2);
+    HIP_CHECK(hipGetLastError());
+    scan_counts(c, cap, nbk, st, cur);  // (the cursors begin at the starts)
+    HIP_CHECK(hipMemsetAsync(ovf, 0, 8, c.stream));
+    rc_partition_gapped_kernel<L2><<<dim3((unsigned)xcd_grid(tiles)), dim3(512), 0, c.stream>>>(
+        (const Key<L2> *)gap.keys, gap.bstart, gap.ustart, tile_g, gap.nb, U, K, hb, cur, dst,
+        (const unsigned long long *)(st + 1), limit, ovf);
+    HIP_CHECK(hipGetLastError());
+    spec_tile_fill_kernel<<<dim3((unsigned)ceil_div(nbk, 256)), dim3(256), 0, c.stream>>>(st, cur, nbk, T2, tv, ntv);
+    HIP_CHECK(hipGetLastError());
+    spec_counts_kernel<<<dim3((unsigned)ceil_div(nbk, 256)), dim3(256), 0, c.stream>>>(st, cur, nbk, rc_hist);
+    HIP_CHECK(hipGetLastError());
+    // the buckets' total and the overflow word in one copy and one wait (the rc sort's level 2 then needs no
+    // read of the keys' ends to plan its buckets: the padded layout spans them all)
+    uint64_t res[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(res, st + nbk, 16, hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+    const uint64_t C = res[0];
+    if (res[1] || C > limit) {
+        if (c.knobs.debug) fprintf(stderr, "[mtg debug] speculative rc level 1: a bucket overflowed, exact histogram pass\n");
+        ++c.timings.spec_fallbacks;
+        c.timings.rc_spec_l1 = 2;
+        HIP_CHECK(hipMemsetAsync(rc_hist, 0, nbk * 4, c.stream));
+        return false;
+    }
+    if (c.knobs.debug)
+        fprintf(stderr, "[mtg debug] speculative rc level 1: U=%lu padded %lu (%.3fx)\n", (unsigned long)U, (unsigned long)C,
+                (double)C / (double)U);
+    c.timings.rc_spec_l1 = 1;
+    *keys_out = dst;
+    *pad = PaddedLayout{C, tv};
+    return true;
+}
+
 // K4: the reverse complements of a sorted canonical set ka[0..U) (add_reverse_complements,
 // boss_chunk_construct.cpp:179-222), sorted on their own.  rc(x) of odd K is never x, so it is a
 // 1:1 map; even K drops the palindromes and doubles their counts (rc_augment_kernel).  `buf`
@@ -926,14 +991,18 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
     uint64_t Urc = U;
     uint32_t *rc_hist = nullptr;
     bool rc_level1 = false;  // buf already partitioned by the rc sort's level-1 digit
+    // ... or the rc keys in speculative level-1 buckets (rc_level1_spec): spec_keys, in the padded layout rc_pad
+    K2 *spec_keys = nullptr;
+    PaddedLayout rc_pad;
     // the fused merge's plan (rc_plan: u128 merge groups twice as full); the plain sort plans its own
     const bool own_plan = rm && L2 == 2 && c.knobs.rc_wide;
     const MsdPlan rcp = own_plan ? rc_plan<L2>(c, U, 2 * K) : MsdPlan{};
     if (K & 1) {
-        unsigned rc_hist_bits = 0;
+        unsigned rc_hist_bits = 0, rc_levels = 0;
         if (!c.knobs.use_lsd && sort) {
             const MsdPlan plan = own_plan ? rcp : msd_plan<L2>(c, U, 2 * K, 1.0);
             if (plan.levels) {
+                rc_levels = plan.levels;
                 rc_hist_bits = plan.digit_end[1];
                 rc_hist = (uint32_t *)c.ws.get(Workspace::HIST1, (1u << rc_hist_bits) * 4);
                 HIP_CHECK(hipMemsetAsync(rc_hist, 0, (1u << rc_hist_bits) * 4, c.stream));
@@ -945,29 +1014,40 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
                 // the canonical set still in its speculative buckets (BuildState::gap): read it there
                 const bool fuse = c.knobs.rc_fuse && rc_hist && rc_hist_bits <= 9 && U;
                 const uint64_t tiles = ceil_div(U, RcPartTraits<L2>::TILE);
-                // (fuse: the histogram only)
-                rc_map_gapped_kernel<L2><<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(c.build.gap.nb, 16), 16384))),
-                                           dim3(256), 0, c.stream>>>((const K2 *)c.build.gap.keys, c.build.gap.bstart, c.build.gap.ustart,
-                                                                     c.build.gap.nb, fuse ? nullptr : buf, K, rc_hist, rc_hist_bits);
-                HIP_CHECK(hipGetLastError());
+                uint64_t *tile_g = nullptr;
                 if (fuse) {
-                    uint64_t *tile_g = (uint64_t *)c.ws.get(Workspace::RC_TILEG, tiles * 8);
+                    tile_g = (uint64_t *)c.ws.get(Workspace::RC_TILEG, tiles * 8);
                     rc_tile_bucket_kernel<<<dim3((unsigned)ceil_div(c.build.gap.nb, 256)), dim3(256), 0, c.stream>>>(
                         c.build.gap.ustart, c.build.gap.nb, RcPartTraits<L2>::TILE, tile_g);
                     HIP_CHECK(hipGetLastError());
+                }
+                // the level-1 buckets sized from a sample (u64 keys; the padded layout needs a level 2 to read
+                // it); an overflow, or MTG_RC_SPEC=0: the exact histogram pass below
+                bool spec = false;
+                if constexpr (L2 == 1) {
+                    if (fuse && c.knobs.rc_spec && rc_levels >= 2 && c.build.gap.nb >= 8)
+                        spec = rc_level1_spec<L2>(c, K, U, rc_hist, rc_hist_bits, tile_g, &spec_keys, &rc_pad);
+                }
+                if (!spec) {
+                    // (fuse: the histogram only)
+                    rc_map_gapped_kernel<L2><<<dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(ceil_div(c.build.gap.nb, 16), 16384))),
+                                               dim3(256), 0, c.stream>>>((const K2 *)c.build.gap.keys, c.build.gap.bstart, c.build.gap.ustart,
+                                                                         c.build.gap.nb, fuse ? nullptr : buf, K, rc_hist, rc_hist_bits);
+                    HIP_CHECK(hipGetLastError());
+                }
+                if (fuse && !spec) {
                     // the histogram above gives the level-1 bucket starts; the rc keys are then written
                     // straight into their level-1 buckets (rc_partition_gapped_kernel)
                     const uint64_t nbk = 1ull << rc_hist_bits;
                     uint64_t *st = (uint64_t *)c.ws.get(Workspace::RC_L1START, (nbk + 1) * 8);
                     auto *cur = (unsigned long long *)c.ws.get(Workspace::RC_L1CUR, nbk * 8);
-                    scan_counts(c, rc_hist, nbk, st);  // fuse: rc_hist_bits <= 9, one block
-                    HIP_CHECK(hipMemcpyAsync(cur, st, nbk * 8, hipMemcpyDeviceToDevice, c.stream));
+                    scan_counts(c, rc_hist, nbk, st, cur);  // fuse: rc_hist_bits <= 9, one block; cur = st
                     rc_partition_gapped_kernel<L2><<<dim3((unsigned)xcd_grid(tiles)), dim3(512), 0, c.stream>>>(
                         (const K2 *)c.build.gap.keys, c.build.gap.bstart, c.build.gap.ustart, tile_g, c.build.gap.nb, U, K, rc_hist_bits, cur,
                         buf);
                     HIP_CHECK(hipGetLastError());
-                    rc_level1 = true;
                 }
+                rc_level1 = fuse;
                 done = true;
             }
         }
@@ -995,6 +1075,7 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
         return Urc;
     }
     K2 *ra = buf, *rb = (K2 *)c.ws.get(Workspace::RC_ALT, Urc * sizeof(K2));
+    if (spec_keys) ra = spec_keys, rb = buf;  // (the speculative buckets are in RC_ALT; buf is the spare)
     uint32_t *rca = bufc, *rcb = COUNTED ? (uint32_t *)c.ws.get(Workspace::RC_ALTC, Urc * 4) : nullptr;
     if (c.knobs.use_lsd) radix_sort<L2, COUNTED>(c, &ra, &rb, &rca, &rcb, Urc, 2 * K, false);
     else {
@@ -1002,6 +1083,7 @@ static uint64_t stage_rc(Ctx &c, unsigned K, unsigned cbits, uint32_t cmax, Key<
         rq.hist1 = rc_hist;
         rq.distinct = true;
         rq.level1_done = rc_level1;
+        rq.gap1 = rc_pad;
         rq.rm = rm;
         rq.force_plan = own_plan && rcp.levels ? &rcp : nullptr;
         Urc = msd_sort_unique<L2, COUNTED>(c, &ra, &rb, &rca, &rcb, Urc, 2 * K, cmax, 1.0, rq);

@@ -365,6 +365,10 @@ struct Knobs {
     bool rc_fuse = true;           // MTG_RC_FUSE=0: the rc keys of a gapped canonical set written in canonical
                                    // order and partitioned by the rc sort's own level 1, not straight into
                                    // its level-1 buckets (rc_partition_gapped_kernel)
+    int rc_spec = 1;               // MTG_RC_SPEC=0: those level-1 buckets sized by an exact histogram pass over the
+                                   // whole canonical set, not from every 8th canonical bucket with slack (the
+                                   // overflow fallback, forced); =tiny: half the estimate, rounded down to whole
+                                   // tiles (tests force the overflow with it)
     bool dummy_bitmap = false;     // MTG_DUMMY_BITMAP=1: the source levels with few real chars as bits of a
                                    // bitmap (dummy_write_kernel) -- the sort gains 0.25 ms, the write pass
                                    // loses as much, so off by default
@@ -452,6 +456,7 @@ static Knobs load_knobs() {
     k.kspec = !is("MTG_KSPEC", "0");
     k.dummy_bitmap = is("MTG_DUMMY_BITMAP", "1");
     k.rc_fuse = !is("MTG_RC_FUSE", "0");
+    k.rc_spec = is("MTG_RC_SPEC", "0") ? 0 : is("MTG_RC_SPEC", "tiny") ? 2 : 1;
     k.spec_l1_tiny = is("MTG_SPEC_L1_CAPS", "tiny");
     if (const char *e = getenv("MTG_SPEC_L1_STRIPES")) {
         const long v = atol(e);

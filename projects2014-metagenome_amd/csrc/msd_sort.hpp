@@ -177,12 +177,14 @@ __global__ __launch_bounds__(256) void hist_rows_reduce_kernel(const uint32_t *_
 
 /*
  * Exclusive scan of u32 counts into u64 starts (starts[n] = total), chained by a wave
- * look-back over tiles of 4096 entries.
+ * look-back over tiles of 4096 entries.  cursors (may be null): starts[0..n) a second time -- the
+ * partition cursors that begin at the bucket starts (a device-to-device copy launch otherwise).
  */
 __global__ __launch_bounds__(512) void scan_counts_kernel(const uint32_t *__restrict__ counts,
                                                           uint64_t n, uint64_t *__restrict__ starts,
                                                           uint64_t *desc, uint32_t epoch,
-                                                          uint32_t *tile_counter, uint32_t *error) {
+                                                          uint32_t *tile_counter, uint32_t *error,
+                                                          unsigned long long *__restrict__ cursors = nullptr) {
     constexpr int ITEMS = 8, TILE = 512 * ITEMS;
     __shared__ uint64_t s_scan[512 / 64 + 1];
     __shared__ uint32_t s_tile;
@@ -202,7 +204,10 @@ __global__ __launch_bounds__(512) void scan_counts_kernel(const uint32_t *__rest
     uint64_t s = s_base + off;
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) {
-        if (i0 + j < n) starts[i0 + j] = s;
+        if (i0 + j < n) {
+            starts[i0 + j] = s;
+            if (cursors) cursors[i0 + j] = s;
+        }
         s += v[j];
     }
     const uint64_t ntiles = (n + TILE - 1) / TILE;

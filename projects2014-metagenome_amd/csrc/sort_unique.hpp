@@ -7,20 +7,23 @@
 
 namespace mtg {
 
-// starts[0..n] = exclusive scan of counts[0..n) (msd_sort.hpp: scan_counts_kernel, one look-back launch)
-static void scan_counts(Ctx &c, const uint32_t *counts, uint64_t n, uint64_t *starts) {
+// starts[0..n] = exclusive scan of counts[0..n) (msd_sort.hpp: scan_counts_kernel, one look-back launch);
+// cursors: starts[0..n) written there too
+static void scan_counts(Ctx &c, const uint32_t *counts, uint64_t n, uint64_t *starts,
+                        unsigned long long *cursors = nullptr) {
     uint32_t ep;
     const uint64_t st = ceil_div(n, 4096);
     uint64_t *desc = acquire_desc(c, st, &ep);
     HIP_CHECK(hipMemsetAsync(&c.small->counter, 0, 4, c.stream));
     scan_counts_kernel<<<dim3((unsigned)st), dim3(512), 0, c.stream>>>(counts, n, starts, desc, ep,
-                                                                      &c.small->counter, &c.small->error);
+                                                                      &c.small->counter, &c.small->error, cursors);
     HIP_CHECK(hipGetLastError());
 }
 
 // the same, then the total read back (a host sync)
-static uint64_t scan_counts_total(Ctx &c, const uint32_t *counts, uint64_t n, uint64_t *starts) {
-    scan_counts(c, counts, n, starts);
+static uint64_t scan_counts_total(Ctx &c, const uint32_t *counts, uint64_t n, uint64_t *starts,
+                                  unsigned long long *cursors = nullptr) {
+    scan_counts(c, counts, n, starts, cursors);
     return read_u64(c, (const unsigned long long *)(starts + n));
 }
 
@@ -302,7 +305,10 @@ struct SortRequest {
 // of slack (a bucket of ~4600 keys overflows with probability ~1e-10 at a 1/8 sample)
 // (buckets outside [blo, bhi) -- below the input's first or above its last previous-level prefix --
 // hold no key and get no slack: a round of a batched collect fills a fraction of the buckets)
-// align (a speculative middle level): capacities rounded up to whole tiles of the next level's tiling
+// align (a speculative middle level, the rc sort's level 1): capacities rounded up to whole tiles of the
+// next level's tiling
+// tiny (tests force the overflow fallback): half the estimate, rounded down to whole tiles under align, so
+// that the rounding never makes room for the other half
 __global__ void spec_caps_kernel(const uint32_t *__restrict__ sample, uint64_t nb, uint32_t stride,
                                  uint32_t *__restrict__ cap, bool tiny, uint64_t blo, uint64_t bhi,
                                  uint32_t align = 0) {
@@ -314,19 +320,20 @@ __global__ void spec_caps_kernel(const uint32_t *__restrict__ sample, uint64_t n
     }
     uint32_t v = tiny ? (uint32_t)(((uint64_t)sample[b] * stride) / 2)
                       : (uint32_t)(((uint64_t)sample[b] * stride * 6) / 5) + 512u;
-    if (align) v = (v + align - 1) / align * align;
+    if (align) v = (tiny ? v : v + align - 1) / align * align;
     cap[b] = v;
 }
 
 // the tile fill of a speculative middle level's output (tile-aligned buckets [bstart[b], bstart[b + 1]),
 // keys up to cur[b]): tile t holds keys in its first tv[t] positions -- the padded-input convention of
-// the next level's kernels (PaddedLayout::tv)
+// the next level's kernels (PaddedLayout::tv).  ntv: the tiles tv holds, where the caller sized it before
+// the buckets' total was known (the rc sort's speculative level 1)
 __global__ void spec_tile_fill_kernel(const uint64_t *__restrict__ bstart, const unsigned long long *__restrict__ cur,
-                                      uint64_t nb, uint32_t tile, uint32_t *__restrict__ tv) {
+                                      uint64_t nb, uint32_t tile, uint32_t *__restrict__ tv, uint64_t ntv = ~0ull) {
     const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nb) return;
     const uint64_t s = bstart[b], e = bstart[b + 1], k = cur[b];
-    for (uint64_t t = s / tile; t < e / tile; ++t) {
+    for (uint64_t t = s / tile; t < min(e / tile, ntv); ++t) {
         const uint64_t t0 = t * tile;
         tv[t] = (uint32_t)(k <= t0 ? 0 : min<uint64_t>(tile, k - t0));
     }
@@ -393,8 +400,9 @@ static uint64_t spec_final_level(Ctx &c, Key<L> **keys, uint32_t **vals, uint64_
             return ~0ull;
         constexpr uint32_t SS = 8;
         constexpr int TILE = MsdTraits<L>::TILE;
-        // after a speculative level-1 layout the input is the padded array (pad)
-        const bool g1 = bp && pad.n && !rm;
+        // after a speculative level-1 layout the input is the padded array (pad): the fused K1's, or the rc
+        // sort's own (stage_rc)
+        const bool g1 = bp && pad.n;
         const uint64_t npos = g1 ? pad.n : n;
         const uint32_t *tv = g1 ? pad.tv : nullptr;
         const uint64_t tiles = ceil_div(npos, TILE);
@@ -444,7 +452,8 @@ static uint64_t spec_final_level(Ctx &c, Key<L> **keys, uint32_t **vals, uint64_
                                                                                         blo, bhi);
         HIP_CHECK(hipGetLastError());
         uint64_t *bstart = (uint64_t *)c.ws.get(Workspace::MSD_BSTART, (nb + 1) * 8);
-        const uint64_t C = scan_counts_total(c, cap, nb, bstart);
+        auto *cur = (unsigned long long *)c.ws.get(Workspace::SPEC_CUR, nb * 8);
+        const uint64_t C = scan_counts_total(c, cap, nb, bstart, cur);  // (the cursors begin at the starts)
         if (spare && C * sizeof(Key<L>) > rq.spec_into_bytes) spare = nullptr;
         if (!spare) {  // the capacity is known now: both slack-sized buffers (one: fused rc merge, in place) must fit
             const uint64_t fr = c.ws.free_bytes();
@@ -461,8 +470,6 @@ static uint64_t spec_final_level(Ctx &c, Key<L> **keys, uint32_t **vals, uint64_
         }
         Key<L> *sa = spare ? spare : (Key<L> *)c.ws.get(Workspace::SPEC_A, C * sizeof(Key<L>));
         uint32_t *sac = COUNTED ? (uint32_t *)c.ws.get(Workspace::SPEC_AC, C * 4) : nullptr;
-        auto *cur = (unsigned long long *)c.ws.get(Workspace::SPEC_CUR, nb * 8);
-        HIP_CHECK(hipMemcpyAsync(cur, bstart, nb * 8, hipMemcpyDeviceToDevice, c.stream));
         HIP_CHECK(hipMemsetAsync(&c.small->spec_ovf, 0, 4, c.stream));
         EventTimer tm(c.stream);
         tm.mark();
@@ -559,6 +566,7 @@ static uint64_t spec_final_level(Ctx &c, Key<L> **keys, uint32_t **vals, uint64_
                 return ~0ull;
             }
             rm->done = true;
+            consumed_gap1();
             ++c.timings.spec_levels;
             if (fine) ++c.timings.spec_fine_levels;
             if (gapped) c.build.gap.valid = false;  // merged: the canonical set is not needed compact
